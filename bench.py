@@ -11,6 +11,11 @@ N GPUs (one process per GPU, torchrun): every rank runs an independent EM restar
 same data -- no data-path collective, weak scaling; value = restarts x iterations / max
 wall time over ranks.
 
+A plain run sets up, runs the warm-up and the timed iterations, writes its outputs if
+--dump-outputs DIR is given, and prints the headline figure.  --full adds a second,
+instrumented fit (kernels_ms, rooflines), the public-API fit_em timing, the CPU baseline
+and, with --decode, decode_latent.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -156,6 +161,39 @@ def cpu_baseline(N, T, L, adam_iters, t_sample=1024, adam_sample=20):
                        f"{adam_sample} Adam bodies timed ({1e3 * t_step:.2f} ms/step, {1e3 * t_body:.2f} ms/body), "
                        f"scaled to T={T} and {adam_iters:.0f} Adam bodies (the GPU run's mean): "
                        f"{total:.0f} s per EM iteration")}
+
+
+DUMP_ROWS = 8192                 # --dump-outputs: time steps of the (T, L) posterior kept
+
+
+def dump_outputs(path, eng, W, stats, lh, logz, n_all):
+    """--dump-outputs: what the last timed EM iteration left on the device, as
+    DIR/<name>.npy (float64, the posterior float32): the M-step's sufficient statistics,
+    fitted weights, Adam record and loss history, the tuning curves, the E-step's
+    posterior marginal over the latent and the log marginal of every iteration of the
+    fit.  The (T, L) posterior is cut to a fixed seeded sample of DUMP_ROWS time steps
+    (sorted; the row numbers are stored beside it), so a dump stays under 64 MB."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    last = n_all - 1
+    T = eng.T
+    rows = np.arange(T) if T <= DUMP_ROWS else np.sort(
+        np.random.default_rng(20240229).choice(T, size=DUMP_ROWS, replace=False))
+    P = eng.P[torch.as_tensor(rows, device=eng.dev)]
+    arrays = {
+        "params": W.cpu().numpy().astype(np.float64),
+        "tuning": eng.tuning64.cpu().numpy().astype(np.float64),
+        "suffstats_yw": eng.yw.cpu().numpy().astype(np.float64),
+        "suffstats_tw": eng.tw.cpu().numpy().astype(np.float64),
+        "adam_stats": stats[last].cpu().numpy().astype(np.float64),
+        "adam_loss_history": lh[last].cpu().numpy().astype(np.float64),
+        "log_marginal": logz[:n_all].cpu().numpy().astype(np.float64),
+        "posterior_latent_marg": P.cpu().numpy().astype(np.float32),
+        "posterior_latent_marg_rows": rows.astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def load_pmc(config):
@@ -366,10 +404,16 @@ def main():
     ap.add_argument("--steps", type=int, default=19, help="timed EM iterations")
     ap.add_argument("--warmup", type=int, default=1, help="untimed leading EM iterations of the same fresh fit")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api-fit", action="store_true", help="skip the public-API fit_em(n_iter=20) timing")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: a second, instrumented fit (kernels_ms, rooflines), the "
+                         "public-API fit_em timing, the CPU baseline and, with --decode, decode_latent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed EM iteration computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-api-fit", action="store_true",
+                    help="--full without the public-API fit_em(n_iter=20) timing")
     ap.add_argument("--decode", action="store_true",
-                    help="also time decode_latent at this config (exact dense and banded paths)")
+                    help="--full: also time decode_latent at this config (exact dense and banded paths)")
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--chunk-bwd", type=int, default=0, help="backward chunk (0: ScanConfig default, 2x forward)")
     ap.add_argument("--warm-steps", type=int, default=48)
@@ -391,6 +435,12 @@ def main():
                     help="CPU-only check of the N-rank launcher: gloo ranks, barrier + max-over-ranks timing of "
                          "a host loop, one JSON line (no GPU is touched)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.decode and not args.full:
+        ap.error("--decode is part of --full")
+    if args.dump_outputs and (args.shard == "time" or args.restarts > 1 or args.launcher_selftest):
+        ap.error("--dump-outputs covers the default path (one restart per GPU)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # N ranks requested without a launcher: start them as children (this process
         # never touches the GPU) and exit with their status
@@ -486,23 +536,22 @@ def main():
         eng.timer = None
         return elapsed, warm_s
 
-    # the measured fit runs uninstrumented; an identical second fresh fit records the
-    # per-section HIP events (kernels_ms, rooflines) -- 18 event records per iteration
-    # are instrumentation, not workload
+    # the measured fit runs uninstrumented
     elapsed, warm_s = timed_fit(None)
-    timer = KernelTimer()
-    elapsed_instrumented, _ = timed_fit(timer)
-    eng.timer = None
-    summ = timer.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, W, stats, lh, logz, n_all)
+    if args.full:
+        # an identical second fresh fit records the per-section HIP events (kernels_ms,
+        # rooflines) -- 18 event records per iteration are instrumentation, not workload
+        timer = KernelTimer()
+        elapsed_instrumented, _ = timed_fit(timer)
+        eng.timer = None
+        summ = timer.summary()
     s = stats.cpu().numpy()
     adam_iters = float(np.mean(s[args.warmup:, 0])) if args.steps else 0.0
     repairs = eng.repairs()
     relax_rounds = eng.relax_rounds()
     lz_host = logz.cpu().numpy()
-
-    pmc, pmc_src = load_pmc(args.config)
-    rooflines = compute_rooflines(summ, T, L, N, B.shape[1], adam_iters, pmc)
-    roof = fwdbwd_roofline(summ, T, L, pmc)
     value = world * args.steps / elapsed
     fresh_s = sum(warm_s) + elapsed
     out = {
@@ -522,17 +571,10 @@ def main():
                                f"one step = one EM iteration of a fresh fit (timed: iterations "
                                f"{args.warmup + 1}..{n_all}, 1-based); ranks = independent restarts",
                    "n_neuron": N, "n_time": T, "n_latent_bin": L, "parallelism": f"restarts x{world}"},
-        "roofline": roof,
-        "rooflines": rooflines,
         "fresh_fit": {"iterations": n_all, "device_s": fresh_s, "em_iters_per_s": n_all / fresh_s,
                       "warmup_iteration_s": [round(v, 5) for v in warm_s],
                       "note": "device-resident EM iterations 1..W+K of one fresh fit (after a one-iteration "
                               "code-object pre-warm), W untimed ones synchronised one by one"},
-        "kernels_ms": {k: round(v[1], 4) for k, v in summ.items()},
-        "kernels_ms_note": "from a second, identical fresh fit with per-section HIP events (the measured fit "
-                           "runs without them)",
-        "ms_per_step_instrumented": 1e3 * elapsed_instrumented / args.steps,
-        "kernel_calls": {k: v[0] for k, v in summ.items()},
         "adam_iters_mean": adam_iters,
         "chunk": eng.C,
         "chunk_bwd": eng.Cb,
@@ -541,14 +583,23 @@ def main():
         "relax_rounds_last": relax_rounds,
         "scan_warmup_fwd_bwd": list(eng.warm),
         "log_marginal_last": float(lz_host[n_all - 1]),
-        "pmc_source": pmc_src,
     }
-    if rank == 0 and world == 1 and not args.no_api_fit:
-        out["fit_em_api"] = api_fit_wall(y, B, W0, lp0, L)
-    if rank == 0 and world == 1 and args.decode:
-        out["decode_latent"] = decode_leg(y, eng.tuning64.cpu().numpy(), L)
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
-        out["cpu_baseline"] = cpu_baseline(N, T, L, adam_iters)
+    if args.full:
+        pmc, pmc_src = load_pmc(args.config)
+        out["roofline"] = fwdbwd_roofline(summ, T, L, pmc)
+        out["rooflines"] = compute_rooflines(summ, T, L, N, B.shape[1], adam_iters, pmc)
+        out["kernels_ms"] = {k: round(v[1], 4) for k, v in summ.items()}
+        out["kernels_ms_note"] = ("from a second, identical fresh fit with per-section HIP events (the measured "
+                                  "fit runs without them)")
+        out["ms_per_step_instrumented"] = 1e3 * elapsed_instrumented / args.steps
+        out["kernel_calls"] = {k: v[0] for k, v in summ.items()}
+        out["pmc_source"] = pmc_src
+        if rank == 0 and world == 1 and not args.no_api_fit:
+            out["fit_em_api"] = api_fit_wall(y, B, W0, lp0, L)
+        if rank == 0 and world == 1 and args.decode:
+            out["decode_latent"] = decode_leg(y, eng.tuning64.cpu().numpy(), L)
+        if rank == 0 and not args.no_cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline(N, T, L, adam_iters)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

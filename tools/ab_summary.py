@@ -1,10 +1,12 @@
-"""Summarise tools/gpu_bench_ab.sh outputs: value and per-section kernel ms per run."""
+"""Summarise tools/gpu_bench_ab.sh outputs (bench.py --full lines): value and per-section
+kernel ms per run.  usage: python tools/ab_summary.py TAG [OUTDIR]"""
 import glob
 import json
 import sys
 
 tag = sys.argv[1]
-for f in sorted(glob.glob(f"gpurun_out/{tag}_*.json")):
+out = sys.argv[2] if len(sys.argv) > 2 else "bench_out"
+for f in sorted(glob.glob(f"{out}/{tag}_*.json")):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:  # noqa: BLE001

@@ -10,7 +10,7 @@ for r in $(seq 1 "$reps"); do
     IFS=, read -r fc bc tw <<< "$c"
     extra=""; [ "$tw" = "tw" ] && extra="--two-waves"
     tag="c${fc}_${bc}${tw:+_$tw}_r$r"
-    timeout -k 10 150 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-api-fit \
+    timeout -k 10 150 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-api-fit \
       --chunk "$fc" --chunk-bwd "$bc" $extra > "$out/$tag.json" 2> "$out/$tag.err" || exit 1
     python - "$out/$tag.json" <<'PY'
 import json, sys
