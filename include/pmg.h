@@ -321,6 +321,42 @@ int pmg_backward_smoother_batched(const float* delta, const float* phi, const fl
                                   size_t workspace_bytes, void* stream, int32_t phase);
 
 /* ------------------------------------------------------------------ */
+/* Most likely (dynamics, latent) path (Viterbi / MAP decoding).  The    */
+/* reference has no Viterbi of its own: the recurrence is                */
+/* decoder.filter_one_step (decoder.py:151-172) with each logsumexp      */
+/* replaced by a max, over the banded device transition above (log K0 =   */
+/* log g[|i-j|] + log invz[i] within the band, -inf beyond it; log K1 =   */
+/* -log L; log A from the f32 A, -inf where A is 0):                      */
+/*   a[d'][i] = max_d (score[d][i] + logA[d,d']),                         */
+/*   score'[0][j] = max_{|i-j|<=band} (a[0][i] + logK0[i,j]) + s*ll[t,j], */
+/*   score'[1][j] = max_i a[1][i] - log L + s*ll[t,j],                    */
+/* score_0 = log_pi0 + s*ll[0], then a back-trace from the arg-max of     */
+/* score_{T-1}.  Ties take the first index in (d, i) order.               */
+/* Emission input as pmg_forward_filter (delta, phi: per-row constants do */
+/* not move an arg-max) plus rblk for the score.  R equal-length          */
+/* sequences are stacked in time: delta (R*T, L), phi / rblk (R*T, nblk), */
+/* sequence r owns rows [r*T, (r+1)*T); one launch covers all of them and */
+/* each sequence's outputs equal its own R = 1 call bit for bit.          */
+/*   log_pi0 (2, L) DEVICE f64: log prior of x_0 (-inf allowed).  The     */
+/*            filters' own t = 0 prior is a uniform state pushed through  */
+/*            one transition: pi0[0,j] = (A00+A10)/(2L) sum_i K0[i,j],    */
+/*            pi0[1,j] = (A01+A11)/(2L); with it log_joint <= the logz    */
+/*            of pmg_forward_filter on the same inputs.                   */
+/* outputs: path_d, path_l (R, T) int32; log_joint (R) f64 =              */
+/*   log p(path, y), the path's terms gathered and summed in f64 in a     */
+/*   fixed order (ll = rblk + delta; log g, log invz, log A from the f32  */
+/*   device values) -- never the scan's f32 scores, which are re-centred  */
+/*   every step and only order the candidates.                            */
+/* Workspace: ~R*T*Lpad bytes of back-pointers (one byte per (t, j) and   */
+/* one int32 per t), Lpad = pmg_fwdbwd_lpad(L); no zero-fill needed.  The */
+/* size is 0 where unsupported (L > 1024, T <= 0, R < 1).                 */
+size_t pmg_viterbi_workspace_size(int64_t T, int32_t L, int32_t R);
+int pmg_viterbi_decode(const float* delta, const float* phi, const double* rblk, int64_t T, int32_t R,
+                       const pmg_transition* tr, const double* log_pi0, double likelihood_scale,
+                       int32_t* path_d, int32_t* path_l, double* log_joint, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ */
 /* Dense log-domain scans: any continuous kernel (custom_transition_kernel,  */
 /* gp_kernel.py:30-34 and 61-66; RBF kernels wider than PMG_MAX_BAND; the     */
 /* latent-only model of decoder_latentonly.py:33-224 with A = [[1,0],[1,0]]). */

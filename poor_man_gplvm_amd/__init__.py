@@ -11,5 +11,6 @@ from .core import (GaussianGPLVM1D, GaussianGPLVMJump1D, PoissonGPLVM1D, Poisson
                    compute_transition_posterior_prob_latent, fit_em_restarts, run_em,
                    run_em_restarts)
 from .engine import AdamConfig, ScanConfig  # noqa: F401
-from .gp_kernel import banded_transition, create_transition_prob_1d, generate_basis  # noqa: F401
+from .gp_kernel import (banded_transition, create_transition_prob_1d, generate_basis,  # noqa: F401
+                        viterbi_log_pi0)
 from . import model_selection_helper, test  # noqa: F401

@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "pmg_dense_lpad", "pmg_dense_state", "pmg_dense_forward_phase", "pmg_dense_backward_phase",
     "pmg_host_alloc", "pmg_host_free", "pmg_copy_d2h",
     "pmg_joint_log_workspace_size", "pmg_joint_log_accumulate_ws", "pmg_posterior_outputs",
+    "pmg_viterbi_workspace_size", "pmg_viterbi_decode",
 )
 
 
@@ -188,6 +189,9 @@ _SIGS = {
                                     _P, _P, _P, _P, _SZ, _P, _I32], _I32),
     "pmg_backward_smoother_batched": ([_P, _P, _P, _I64, _I32, ctypes.POINTER(Transition), _D, _I32, _I32, _D,
                                        _P, _P, _P, _SZ, _P, _I32], _I32),
+    "pmg_viterbi_workspace_size": ([_I64, _I32, _I32], _SZ),
+    "pmg_viterbi_decode": ([_P, _P, _P, _I64, _I32, ctypes.POINTER(Transition), _P, _D, _P, _P, _P, _P, _SZ, _P],
+                           _I32),
 }
 
 _lib = None

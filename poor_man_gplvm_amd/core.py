@@ -417,6 +417,77 @@ class PoissonGPLVMJump1D:
                 'log_one_step_predictive_marginals_all': _np(eng.logc).astype(np.float32),
                 'posterior_dynamics_marg': _np(posterior_outputs(gamma, log=False)[2])}
 
+    def decode_latent_viterbi(self, y, tuning=None, hyperparam={}, ma_neuron=None, ma_latent=None,
+                              likelihood_scale=1., n_time_per_chunk=10000, t_l=None):
+        """The jointly most likely (dynamics, latent) path given y (MAP / Viterbi decoding):
+        argmax_x log p(x, y) with
+          log p(x, y) = log pi0[x_0] + sum_{t>=1} (logA[d_{t-1}, d_t] + logK[d_t][l_{t-1}, l_t])
+                        + sum_t likelihood_scale * ll[t, l_t]
+        over the banded device transition (continuous moves beyond the kernel's band have
+        probability exactly 0) and the filters' own t = 0 prior (gp_kernel.viterbi_log_pi0),
+        so log_joint_map <= log_marginal_final of the same decode.  The reference has no
+        Viterbi; the recurrence is decoder.filter_one_step (decoder.py:151-172) with max in
+        place of logsumexp (pmg_viterbi_decode).  Defaults and hyper-parameter overrides as
+        decode_latent; n_time_per_chunk is accepted and unused.
+
+        y (T, N), or (R, T, N): R equal-length sequences decoded in one launch, each
+        result equal to its own single-sequence call bit for bit.
+        Returns {'map_dynamics': (T,) int32, 'map_latent': (T,) int32, 'log_joint_map': float}
+        (a leading R and an (R,) log_joint_map for batched input; the latent-only models
+        omit map_dynamics).  A transition that needs the dense scans (custom kernel,
+        n_latent_bin > 1024, band > 32) raises NotImplementedError before any device work."""
+        if _is_tsd(y):
+            t_l = y.t
+            y = y.d
+        hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
+        tr = self._map_transition(hp)          # host-only: raises for a dense transition
+        if tuning is None:
+            tuning = self.tuning
+        if ma_neuron is None:
+            ma_neuron = self.ma_neuron_default
+        if ma_latent is None:
+            ma_latent = self.ma_latent_default
+        y = y if isinstance(y, torch.Tensor) else np.asarray(y)
+        if y.ndim not in (2, 3):
+            raise ValueError(f"y must be (n_time, n_neuron) or (n_seq, n_time, n_neuron), got {tuple(y.shape)}")
+        R = int(y.shape[0]) if y.ndim == 3 else 0
+        if R:
+            if ma_neuron is not None and np.ndim(ma_neuron) != 1:
+                raise ValueError("batched sequences take a 1-D ma_neuron")
+            y = y.reshape(y.shape[0] * y.shape[1], y.shape[2])
+        eng = self._decode_engine(y, tuning, hp, ma_neuron, ma_latent, exact=False)
+        if eng.dense:       # the latent-only models' smoother transition; the MAP path takes the band
+            eng.set_transition(tr)
+        eng.emission(likelihood_scale)
+        pd, pl, lj = eng.viterbi(likelihood_scale, max(R, 1))
+        eng.check_status()
+        pd, pl, lj = _np(pd), _np(pl), _np(lj)
+        if not R:
+            pd, pl, lj = pd[0], pl[0], float(lj[0])
+        return self._viterbi_result(pd, pl, lj, t_l)
+
+    def _map_transition(self, hyperparam):
+        """The banded transition decode_latent_viterbi maximises over, from host arithmetic
+        alone; NotImplementedError (naming the cause) where these hyper-parameters need
+        the dense scans."""
+        mv = hyperparam.get('movement_variance', self.movement_variance)
+        pmj = hyperparam.get('p_move_to_jump', self.p_move_to_jump)
+        pjm = hyperparam.get('p_jump_to_move', self.p_jump_to_move)
+        try:
+            return banded_transition(self.n_latent_bin, mv, pmj, pjm, custom_kernel=self.custom_transition_kernel)
+        except NotImplementedError as e:
+            raise NotImplementedError("decode_latent_viterbi runs on the banded transition only (a dense "
+                                      f"transition kernel is not supported): {e}") from None
+
+    def _viterbi_result(self, path_d, path_l, log_joint, t_l=None):
+        """decode_latent_viterbi's returned dict.  With pynapple and time stamps the two
+        paths are wrapped by the rule _decode_result uses for the marginals (a Tsd each: they
+        are 1-D); pynapple is not installed in the test image, so that branch is untested."""
+        if t_l is not None and nap is not None and path_l.ndim == 1:
+            path_d = nap.Tsd(d=path_d, t=t_l)
+            path_l = nap.Tsd(d=path_l, t=t_l)
+        return {'map_dynamics': path_d, 'map_latent': path_l, 'log_joint_map': log_joint}
+
     def _decode_result(self, r, t_l=None):
         """decode_latent's returned dict from a _decode_on result (core.py:477-497)."""
         posterior_all = r['posterior_all']
@@ -1243,6 +1314,12 @@ class PoissonGPLVM1D(PoissonGPLVMJump1D):
         mv = hp.get('movement_variance', self.movement_variance)
         _, logK, _, logA = create_transition_prob_1d(self.n_latent_bin, mv, 0.0, 1.0, self.custom_transition_kernel)
         return hp, logK, logA
+
+    def _viterbi_result(self, path_d, path_l, log_joint, t_l=None):
+        """No dynamics in the latent-only models: the path never leaves d = 0."""
+        r = super()._viterbi_result(path_d, path_l, log_joint, t_l)
+        del r['map_dynamics']
+        return r
 
     def _decode_result(self, r, t_l=None):
         """decode_latent's latent-only dict (core.py:160-177)."""

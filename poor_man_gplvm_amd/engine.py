@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .gp_kernel import BandedTransition, DenseTransition, banded_transition
+from .gp_kernel import BandedTransition, DenseTransition, banded_transition, viterbi_log_pi0
 
 
 def _ru(x, m):
@@ -858,6 +858,33 @@ class DeviceEM:
             nat.check(self.lib.pmg_backward_smoother_phase(*args, 1 | ad | self._tw_bits()), "pmg_backward_smoother")
         with self._t('backward_repair'):         # verify / relaxation
             nat.check(self.lib.pmg_backward_smoother_phase(*args, 2 | ad | self._seg_bits()), "pmg_backward_smoother")
+
+    def viterbi(self, likelihood_scale, n_seq=1):
+        """Most likely (dynamics, latent) path under the banded transition
+        (pmg_viterbi_decode), after emission() with the same likelihood_scale.  n_seq > 1:
+        the spikes are n_seq equal-length sequences stacked in time, decoded in one launch.
+        Returns device tensors path_d, path_l (n_seq, T / n_seq) int32 and log_joint
+        (n_seq,) float64."""
+        if self.dense or self._tr_c is None:
+            raise NotImplementedError("viterbi needs a banded transition (set_transition with a BandedTransition)")
+        R = int(n_seq)
+        if R < 1 or self.T % R:
+            raise ValueError("stacked sequences must have equal length")
+        T = self.T // R
+        need = int(self.lib.pmg_viterbi_workspace_size(T, self.L, R))
+        if need == 0:
+            raise nat.NativeError(f"pmg_viterbi_workspace_size(T={T}, L={self.L}, R={R}) returned 0")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        log_pi0 = torch.as_tensor(viterbi_log_pi0(self._tr), device=self.dev)
+        path_d = torch.empty((R, T), dtype=torch.int32, device=self.dev)
+        path_l = torch.empty((R, T), dtype=torch.int32, device=self.dev)
+        lj = torch.empty(R, dtype=torch.float64, device=self.dev)
+        with self._t('viterbi'):
+            nat.check(self.lib.pmg_viterbi_decode(nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.rblk), T, R,
+                                                  ctypes.byref(self._tr_c), nat.ptr(log_pi0), float(likelihood_scale),
+                                                  nat.ptr(path_d), nat.ptr(path_l), nat.ptr(lj), nat.ptr(ws),
+                                                  ws.numel(), nat.stream_handle()), "pmg_viterbi_decode")
+        return path_d, path_l, lj
 
     def e_step(self, likelihood_scale, logz_out, gamma=None, rho=None, log_gamma=None, keep_alpha=None):
         """keep_alpha (default: whenever a posterior output is requested): write alpha in full."""

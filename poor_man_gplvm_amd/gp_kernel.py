@@ -122,6 +122,25 @@ def banded_transition(n_latent_bin, movement_variance=1.0, p_move_to_jump=0.01,
                             A=A, movement_variance=mv)
 
 
+def viterbi_log_pi0(tr: BandedTransition) -> np.ndarray:
+    """(2, L) float64 log prior of the first state of the MAP path: the filters' own t = 0
+    prior, a uniform (d, l) state "at t = -1" pushed through one transition with a sum,
+      pi0[0, j] = (A00 + A10) / (2L) * sum_i K0[i, j],   pi0[1, j] = (A01 + A11) / (2L),
+    over the device transition (K0[i, j] = g[|i-j|] * invz[i] within the band, exactly 0
+    beyond it; g, invz and A at their float32 device values).  log 0 = -inf."""
+    L, band = int(tr.L), int(tr.band)
+    g = np.asarray(tr.g, np.float32).astype(np.float64)
+    invz = np.asarray(tr.invz, np.float32).astype(np.float64)
+    A = np.asarray(tr.A, np.float64).astype(np.float32).astype(np.float64)
+    col = np.zeros(L)
+    for k in range(-band, band + 1):          # i = j + k
+        lo, hi = max(0, -k), min(L, L - k)
+        col[lo:hi] += g[abs(k)] * invz[lo + k:hi + k]
+    pi0 = np.stack([(A[0, 0] + A[1, 0]) / (2 * L) * col, np.full(L, (A[0, 1] + A[1, 1]) / (2 * L))])
+    with np.errstate(divide='ignore'):
+        return np.log(pi0)
+
+
 @dataclass
 class DenseTransition:
     """Full log-domain device description: logK0 (L, L) [i_prev, j_next] (row-normalised,
