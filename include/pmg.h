@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PMG_ABI_VERSION 2
+#define PMG_ABI_VERSION 3
 
 #define PMG_OK 0
 #define PMG_EINVAL (-1)       /* bad shape / argument */
@@ -355,6 +355,45 @@ int pmg_viterbi_decode(const float* delta, const float* phi, const double* rblk,
                        const pmg_transition* tr, const double* log_pi0, double likelihood_scale,
                        int32_t* path_d, int32_t* path_l, double* log_joint, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ */
+/* Smoother of many short, independent chains (events: ripple or replay  */
+/* candidates, trials, epochs) in one call: decoder.filter_one_step       */
+/* (decoder.py:151-172) scanned by filter_all_step (:174-187) and         */
+/* smooth_one_step (:200-226) scanned by smooth_all_step (:230-256), once  */
+/* per segment (decoder.py:151-256), with no state carried from one        */
+/* segment to the next.  One wave per segment walks it sequentially and    */
+/* exactly (no chunks, warm-up or verification: no workspace, tol or       */
+/* chunk), with the step arithmetic of pmg_forward_filter /                */
+/* pmg_backward_smoother, banded transitions only.                         */
+/*   delta, phi, m: the emission of T gathered rows, exactly as            */
+/*            pmg_forward_filter takes them (pmg_emission_*, then          */
+/*            pmg_emission_rowref);                                        */
+/*   seg_off  (S+1) DEVICE int64 row offsets: segment s owns rows          */
+/*            [seg_off[s], seg_off[s+1]).  The entry point cannot read     */
+/*            them: the kernels clamp each segment to 0 <= a <= b <= T,    */
+/*            and an empty one (a >= b) only gets logz[s] = 0;             */
+/*   order    (S) DEVICE int32, or NULL: workgroup b processes segment     */
+/*            order[b] (NULL: b).  Pass the segments longest first so that */
+/*            the long ones do not form the tail of the launch; it changes */
+/*            scheduling only, never a value (a permutation of 0 .. S-1;   */
+/*            entries outside it are skipped).                             */
+/* The first row's prior of every segment is the filters' own: a uniform   */
+/* (d, l) state pushed through one transition.                             */
+/* outputs: alpha (T,2,L) f32 filter posteriors (required: the backward    */
+/*          pass reads them back); gamma (T,2,L) f32 or NULL; P (T,L) f32  */
+/*          = sum_d gamma, or NULL (both NULL: forward only);              */
+/*          logc (T) f64 one-step predictive marginals (decoder.py:167);   */
+/*          logz (S) f64, logz[s] = the segment's logc summed in time      */
+/*          order (decoder.py:169).                                        */
+/* Rows that no segment owns are not written.  A segment's outputs do not  */
+/* depend on which other segments are in the call, on their order, or on   */
+/* `order`.  PMG_EUNSUPPORTED for L > 1024.                                */
+int pmg_segment_smoother(const float* delta, const float* phi, const double* m, int64_t T,
+                         const int64_t* seg_off, int32_t S, const int32_t* order,
+                         const pmg_transition* tr, double likelihood_scale,
+                         float* alpha, float* gamma, float* P, double* logc, double* logz,
+                         void* stream);
 
 /* ------------------------------------------------------------------ */
 /* Dense log-domain scans: any continuous kernel (custom_transition_kernel,  */

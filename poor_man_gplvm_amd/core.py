@@ -466,17 +466,98 @@ class PoissonGPLVMJump1D:
             pd, pl, lj = pd[0], pl[0], float(lj[0])
         return self._viterbi_result(pd, pl, lj, t_l)
 
-    def _map_transition(self, hyperparam):
-        """The banded transition decode_latent_viterbi maximises over, from host arithmetic
-        alone; NotImplementedError (naming the cause) where these hyper-parameters need
-        the dense scans."""
+    def decode_latent_segments(self, y, segments=None, tuning=None, hyperparam={}, ma_neuron=None,
+                               ma_latent=None, likelihood_scale=1.):
+        """Smooth many independent events (ripple or replay candidates, trials, epochs) in
+        one call: each segment is a chain of its own, started from the filters' own prior
+        (a uniform (d, l) state pushed through one transition), with no state carried
+        across the gaps -- what decode_latent gives on each segment alone (decoder.py:151-256
+        per segment; the reference loops over epochs, reactivation_analysis.decode_pre_post).
+
+        y (T, N) with segments (S, 2) integer [start, stop) row intervals
+        (0 <= start < stop <= T; unsorted and overlapping ones are fine), or a list of
+        (T_s, N) arrays with segments=None.  The rows are gathered into one compact array in
+        the order given; one emission serves all events and one wave per event walks it
+        (pmg_segment_smoother).  An event longer than scan_config.segment_wave_max rows is
+        decoded on its own by the chunk-parallel scans and spliced into the same arrays.
+        Defaults and hyper-parameter overrides as decode_latent; a 2-D ma_neuron (T, N) is
+        gathered with y (not available with list input).
+
+        Returns a dict; segment s is rows segment_offsets[s]:segment_offsets[s + 1] of
+          segment_offsets (S + 1,) int64, posterior_all (Ttot, 2, L),
+          posterior_latent_marg (Ttot, L), posterior_dynamics_marg (Ttot, 2),
+          log_causal_posterior_all (Ttot, 2, L), log_one_step_predictive_marginals_all (Ttot,),
+          log_likelihood_all (Ttot, L), log_marginal_final (S,) float64.
+        The pairwise joint (p_transition_*) is not formed.  A transition that needs the dense
+        scans (custom kernel, n_latent_bin > 1024, band > 32) raises NotImplementedError, and
+        bad intervals ValueError, before any device work."""
+        if _is_tsd(y):
+            y = y.d
+        hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
+        self._map_transition(hp, 'decode_latent_segments')      # host-only: raises for a dense transition
+        if ma_neuron is None:
+            ma_neuron = self.ma_neuron_default
+        yc, off, ma = gather_segments(y, segments, ma_neuron)
+        if tuning is None:
+            tuning = self.tuning
+        if ma_latent is None:
+            ma_latent = self.ma_latent_default
+        S, Ttot, L = len(off) - 1, int(off[-1]), self.n_latent_bin
+        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
+        dev = eng.dev
+        cp = _PinnedCopies(dev)
+        for key, shape in (('lcaus', (Ttot, 2, L)), ('gamma', (Ttot, 2, L)), ('ll', (Ttot, L)), ('plm', (Ttot, L))):
+            cp.reserve(key, shape)
+        gamma = torch.empty((Ttot, 2, L), dtype=torch.float32, device=dev)
+        logz = torch.empty(S, dtype=torch.float64, device=dev)
+        eng.emission(likelihood_scale)
+        short = np.diff(off) <= int(self.scan_config.segment_wave_max)
+        for i0, i1 in _true_runs(short):       # consecutive one-wave segments: one call per run
+            r0, r1 = int(off[i0]), int(off[i1])
+            rel = off[i0:i1 + 1] - r0
+            _, _, lz = eng.segment_smoother(likelihood_scale, torch.as_tensor(rel, device=dev),
+                                            torch.as_tensor(segment_order(rel), device=dev),
+                                            gamma=gamma[r0:r1], rows=(r0, r1))
+            logz[i0:i1] = lz
+        for i in np.flatnonzero(~short):        # the chunk-parallel scans, one segment at a time
+            a, b = int(off[i]), int(off[i + 1])
+            sub = self._decode_engine(yc[a:b], tuning, hp, ma[a:b] if np.ndim(ma) == 2 else ma, ma_latent,
+                                      exact=False)
+            sub.e_step(likelihood_scale, logz[i:i + 1], gamma=gamma[a:b])
+            sub.check_status()
+            eng.alpha[a:b].copy_(sub.alpha)
+            eng.logc[a:b].copy_(sub.logc)
+        eng.check_status()
+        ml = None if ma_latent is None else np.asarray(ma_latent).astype(bool)
+        _, plm, pdm = posterior_outputs(gamma, log=False)
+        h_lcaus = cp.submit(log_of(eng.alpha), key='lcaus')
+        h_gamma = cp.submit(gamma, key='gamma')
+        h_plm = cp.submit(plm, key='plm')
+        h_pdm = cp.submit(pdm)
+        h_logc = cp.submit(eng.logc.to(torch.float32))
+        h_ll = cp.submit(eng.loglik(), key='ll')
+        h_lz = cp.submit(logz)
+        cp.finish()
+        return {'segment_offsets': off,
+                'posterior_all': h_gamma,
+                'posterior_latent_marg': h_plm,
+                'posterior_dynamics_marg': h_pdm,
+                'log_causal_posterior_all': _masked_log(h_lcaus, ml),
+                'log_one_step_predictive_marginals_all': h_logc,
+                'log_likelihood_all': h_ll,
+                'log_marginal_final': h_lz}
+
+    def _map_transition(self, hyperparam, what='decode_latent_viterbi'):
+        """The banded transition decode_latent_viterbi maximises over (and
+        decode_latent_segments smooths with), from host arithmetic alone; NotImplementedError
+        (naming the cause) where these hyper-parameters need the dense scans."""
         mv = hyperparam.get('movement_variance', self.movement_variance)
         pmj = hyperparam.get('p_move_to_jump', self.p_move_to_jump)
         pjm = hyperparam.get('p_jump_to_move', self.p_jump_to_move)
         try:
             return banded_transition(self.n_latent_bin, mv, pmj, pjm, custom_kernel=self.custom_transition_kernel)
         except NotImplementedError as e:
-            raise NotImplementedError("decode_latent_viterbi runs on the banded transition only (a dense "
+            raise NotImplementedError(f"{what} runs on the banded transition only (a dense "
                                       f"transition kernel is not supported): {e}") from None
 
     def _viterbi_result(self, path_d, path_l, log_joint, t_l=None):
@@ -769,6 +850,67 @@ class PoissonGPLVMJump1D:
 # value when the smoothed ratio is flat) instead of NaN.  Probability-space outputs
 # differ from the reference by < 1e-290 there.
 JOINT_COUNT_FLOOR = 1e-300
+
+
+def gather_segments(y, segments=None, ma_neuron=None):
+    """The compact layout of decode_latent_segments, on the host: (y_compact (Ttot, N)
+    float32, offsets (S + 1,) int64, ma_neuron).  y (T, N) with segments (S, 2) integer
+    [start, stop) rows, 0 <= start < stop <= T, gathered in the order given (a 2-D
+    ma_neuron (T, N) is gathered with them), or a list of (T_s, N) arrays with
+    segments=None (concatenated; a 2-D ma_neuron is refused).  ValueError otherwise."""
+    if segments is None:
+        if not isinstance(y, (list, tuple)) or len(y) == 0:
+            raise ValueError("segments=None takes a non-empty list of (T_s, n_neuron) arrays")
+        parts = [np.asarray(a) for a in y]
+        for k, a in enumerate(parts):
+            if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != parts[0].shape[1]:
+                raise ValueError(f"segment {k}: expected a non-empty (T_s, {parts[0].shape[-1]}) array, got "
+                                 f"{tuple(a.shape)}")
+        if ma_neuron is not None and np.ndim(ma_neuron) != 1:
+            raise ValueError("a list of segments takes a 1-D ma_neuron")
+        lens = np.array([a.shape[0] for a in parts], np.int64)
+        yc = np.concatenate(parts).astype(np.float32)
+    else:
+        y = np.asarray(y)
+        if y.ndim != 2:
+            raise ValueError(f"y must be (n_time, n_neuron), got {tuple(y.shape)}")
+        seg = np.asarray(segments)
+        if seg.ndim != 2 or seg.shape[1] != 2 or seg.shape[0] < 1:
+            raise ValueError(f"segments must be (n_segment, 2) [start, stop) rows, got {tuple(seg.shape)}")
+        if not np.issubdtype(seg.dtype, np.integer):
+            if not (np.issubdtype(seg.dtype, np.floating) and np.all(seg == np.floor(seg))):
+                raise ValueError("segments must hold integer row indices")
+        seg = seg.astype(np.int64)
+        T = y.shape[0]
+        bad = np.flatnonzero((seg[:, 0] < 0) | (seg[:, 0] >= seg[:, 1]) | (seg[:, 1] > T))
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"segment {k}: [{seg[k, 0]}, {seg[k, 1]}) is empty or outside [0, {T}]")
+        lens = seg[:, 1] - seg[:, 0]
+        idx = np.concatenate([np.arange(a, b) for a, b in seg])
+        yc = np.ascontiguousarray(y[idx], dtype=np.float32)
+        if ma_neuron is not None and np.ndim(ma_neuron) == 2:
+            ma_neuron = np.asarray(ma_neuron)
+            if ma_neuron.shape != y.shape:
+                raise ValueError(f"2-D ma_neuron must be {tuple(y.shape)}, got {tuple(ma_neuron.shape)}")
+            ma_neuron = np.ascontiguousarray(ma_neuron[idx])
+    off = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    return yc, off, ma_neuron
+
+
+def segment_order(offsets):
+    """(S,) int32: the segments of CSR `offsets` longest first (ties in index order), the
+    workgroup order of pmg_segment_smoother."""
+    lens = np.diff(np.asarray(offsets, np.int64))
+    return np.argsort(-lens, kind='stable').astype(np.int32)
+
+
+def _true_runs(mask):
+    """[(i0, i1)]: the maximal runs mask[i0:i1] of True."""
+    m = np.concatenate([[False], np.asarray(mask, bool), [False]])
+    d = np.flatnonzero(m[1:] != m[:-1])
+    return list(zip(d[::2].tolist(), d[1::2].tolist()))
 
 
 def log_joint_from_counts(S4, logK, logA, ml=None):
@@ -1307,6 +1449,14 @@ class PoissonGPLVM1D(PoissonGPLVMJump1D):
         hp, logK, logA = self._dynamics_decode_args(hyperparam)
         r = self._run_decode(y, tuning, hp, ma_neuron, ma_latent, likelihood_scale, joint=True, logK=logK, logA=logA)
         return self._decode_result(r, t_l)
+
+    def decode_latent_segments(self, y, segments=None, **kwargs):
+        """Not available: the one-wave segment smoother runs the banded linear-space scans,
+        and a chain without a jump path is ill-conditioned in float32 (see _transition: the
+        latent-only models always take the dense log-domain scans)."""
+        raise NotImplementedError(f"{type(self).__name__}.decode_latent_segments: the latent-only models need the "
+                                  "dense log-domain scans, which the segment smoother does not run; call "
+                                  "decode_latent once per segment")
 
     def _dynamics_decode_args(self, hyperparam):
         hp = dict(hyperparam)

@@ -1647,4 +1647,52 @@ PMG_FB_ALL(PMG_FB_DECL)
 #define PMG_FB_INST(JJ, WPP) \
   void fb_set_j##JJ##_w##WPP(FBKernelSet* k) { fb_fill<JJ, WPP>(k); }
 
+// ---------------------------------------------------------------------------
+// host: the parameters every banded scan shares (fwdbwd.hip, segments.hip)
+// ---------------------------------------------------------------------------
+// latents per lane (Lpad = 64 J), -1 beyond 1024
+static inline int pick_J(int L) {
+  if (L <= 64) return 1;
+  if (L <= 128) return 2;
+  if (L <= 256) return 4;
+  if (L <= 512) return 8;
+  if (L <= 1024) return 16;
+  return -1;
+}
+static inline int fill_params(FBParams& p, const pmg_transition* tr, int64_t T, int C, int B, double s,
+                              double tol) {
+  PMG_REQUIRE(tr && tr->L > 0 && tr->invz, "pmg fwd/bwd: bad transition");
+  PMG_REQUIRE(tr->band >= 0 && tr->band <= kMaxBand,
+              "pmg fwd/bwd: continuous-kernel band %d > %d unsupported (dense kernels: not yet)",
+              tr->band, kMaxBand);
+  PMG_REQUIRE(T > 0 && C > 0 && B >= 0, "pmg fwd/bwd: T=%lld chunk=%d warmup=%d", (long long)T, C, B);
+  const int J = pick_J(tr->L);
+  PMG_REQUIRE(J > 0, "pmg fwd/bwd: L=%d > 1024 unsupported", tr->L);
+  memset(&p, 0, sizeof(p));
+  p.T = T;
+  p.L = tr->L;
+  p.nblk = (int)(round_up(tr->L, 32) / 32);
+  p.invz = tr->invz;
+  p.A00 = tr->A[0];
+  p.A01 = tr->A[1];
+  p.A10 = tr->A[2];
+  p.A11 = tr->A[3];
+  p.invL = 1.f / (float)tr->L;
+  p.s = (float)s;
+  p.s_d = s;
+  p.C = C;
+  p.B = B;
+  p.M = (int)((T + C - 1) / C);
+  p.tol = (float)tol;
+  p.Lpad = 64 * J;
+  p.ldd = p.L;
+  p.ldphi = p.nblk;
+  p.ldm = 1;
+  p.ws_stride = 0;
+  p.adapt = 0;
+  p.spin = spin_ticks(kSpinTicks);
+  for (int k = 0; k <= kMaxBand; ++k) p.g[k] = (k <= tr->band) ? tr->g[k] : 0.f;
+  return PMG_OK;
+}
+
 }  // namespace pmg

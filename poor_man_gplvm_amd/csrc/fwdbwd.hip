@@ -110,14 +110,6 @@ static void relax_shape(FBParams& p) {
 // pending word, so the relaxation kernel repairs nothing (it only sums logZ).
 static bool debug_no_repair() { return getenv("PMG_DEBUG_NO_REPAIR") != nullptr; }
 
-static int pick_J(int L) {
-  if (L <= 64) return 1;
-  if (L <= 128) return 2;
-  if (L <= 256) return 4;
-  if (L <= 512) return 8;
-  if (L <= 1024) return 16;
-  return -1;
-}
 // band = ceil(8.31 mv): 5 (mv 0.5), 9 (mv 1, the default), 17 (mv 2), 25 (mv 3) are exact
 static int pick_WP(int band) {
   if (band <= 5) return 5;
@@ -139,42 +131,6 @@ static bool fb_set(int J, int WP, FBKernelSet* k) {
   PMG_FB_ALL(PMG_FB_CASE)
 #undef PMG_FB_CASE
   return false;
-}
-
-static int fill_params(FBParams& p, const pmg_transition* tr, int64_t T, int C, int B,
-                       double s, double tol) {
-  PMG_REQUIRE(tr && tr->L > 0 && tr->invz, "pmg fwd/bwd: bad transition");
-  PMG_REQUIRE(tr->band >= 0 && tr->band <= kMaxBand,
-              "pmg fwd/bwd: continuous-kernel band %d > %d unsupported (dense kernels: not yet)",
-              tr->band, kMaxBand);
-  PMG_REQUIRE(T > 0 && C > 0 && B >= 0, "pmg fwd/bwd: T=%lld chunk=%d warmup=%d", (long long)T, C, B);
-  const int J = pick_J(tr->L);
-  PMG_REQUIRE(J > 0, "pmg fwd/bwd: L=%d > 1024 unsupported", tr->L);
-  memset(&p, 0, sizeof(p));
-  p.T = T;
-  p.L = tr->L;
-  p.nblk = (int)(round_up(tr->L, 32) / 32);
-  p.invz = tr->invz;
-  p.A00 = tr->A[0];
-  p.A01 = tr->A[1];
-  p.A10 = tr->A[2];
-  p.A11 = tr->A[3];
-  p.invL = 1.f / (float)tr->L;
-  p.s = (float)s;
-  p.s_d = s;
-  p.C = C;
-  p.B = B;
-  p.M = (int)((T + C - 1) / C);
-  p.tol = (float)tol;
-  p.Lpad = 64 * J;
-  p.ldd = p.L;
-  p.ldphi = p.nblk;
-  p.ldm = 1;
-  p.ws_stride = 0;
-  p.adapt = 0;
-  p.spin = spin_ticks(kSpinTicks);
-  for (int k = 0; k <= kMaxBand; ++k) p.g[k] = (k <= tr->band) ? tr->g[k] : 0.f;
-  return PMG_OK;
 }
 
 // R > 1: R restarts' latents stacked side by side in delta / phi / m (and P), each

@@ -86,6 +86,13 @@ class ScanConfig:
                                   # underflow, and the far kernel entries the band drops decide them).
                                   # False: the banded linear-space scans (faster; those rows fall back
                                   # to the prior transition, core.JOINT_COUNT_FLOOR)
+    segment_wave_max: int = 1024  # decode_latent_segments: a segment of up to this many rows is walked by
+                                  # one wave of pmg_segment_smoother; a longer one is decoded on its own by
+                                  # the chunk-parallel scans.  The largest power of two at which the
+                                  # one-wave route was not slower for a single segment at the C3 shape:
+                                  # 6.0 against 6.8 ms per call at 1024 rows, 11.8 against 8.0 ms at 4096
+                                  # (one wave takes ~1.35 us per row, the chunk-parallel route pays a second
+                                  # engine and emission; profiles/segments_crossover_c3.json)
 
     def chunk_for(self, T):
         if self.chunk:
@@ -885,6 +892,42 @@ class DeviceEM:
                                                   nat.ptr(path_d), nat.ptr(path_l), nat.ptr(lj), nat.ptr(ws),
                                                   ws.numel(), nat.stream_handle()), "pmg_viterbi_decode")
         return path_d, path_l, lj
+
+    def segment_smoother(self, likelihood_scale, seg_off, order=None, gamma=None, P=None, rows=None):
+        """Filter and smooth independent segments of the rows in one call (pmg_segment_smoother:
+        one wave per segment, exact and sequential), after emission() with the same
+        likelihood_scale.  seg_off: (S + 1,) int64 device row offsets, segment s owning rows
+        [seg_off[s], seg_off[s + 1]); order: (S,) int32 device tensor, the segment each
+        workgroup takes (longest first; scheduling only), or None; gamma (T, 2, L) / P (T, L)
+        float32 device outputs or None.  rows = (r0, r1): the call sees only rows [r0, r1) of
+        the engine (offsets and outputs relative to r0).  Returns device tensors
+        (alpha (T, 2, L) -- the engine's buffer --, logc (T,), logz (S,) float64); rows that no
+        segment owns are left as they were."""
+        if self.dense or self._tr_c is None:
+            raise NotImplementedError("segment_smoother needs a banded transition (set_transition with a "
+                                      "BandedTransition)")
+        r0, r1 = (0, self.T) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 < r1 <= self.T:
+            raise ValueError(f"rows {(r0, r1)} outside [0, {self.T}]")
+        T = r1 - r0
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
+            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
+        S = seg_off.numel() - 1
+        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
+            raise ValueError(f"order must be a ({S},) int32 device tensor")
+        for name, t, shape in (('gamma', gamma, (T, 2, self.L)), ('P', P, (T, self.L))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
+                raise ValueError(f"{name} must be a {shape} float32 device tensor")
+        logz = torch.empty(S, dtype=torch.float64, device=self.dev)
+        alpha, logc = self.alpha[r0:r1], self.logc[r0:r1]
+        with self._t('segment_smoother'):
+            nat.check(self.lib.pmg_segment_smoother(nat.ptr(self.delta[r0:r1]), nat.ptr(self.phi[r0:r1]),
+                                                    nat.ptr(self.mref[r0:r1]), T, nat.ptr(seg_off), S, nat.ptr(order),
+                                                    ctypes.byref(self._tr_c), float(likelihood_scale),
+                                                    nat.ptr(alpha), nat.ptr(gamma), nat.ptr(P), nat.ptr(logc),
+                                                    nat.ptr(logz), nat.stream_handle()), "pmg_segment_smoother")
+        self.alpha_bits = 0
+        return alpha, logc, logz
 
     def e_step(self, likelihood_scale, logz_out, gamma=None, rho=None, log_gamma=None, keep_alpha=None):
         """keep_alpha (default: whenever a posterior output is requested): write alpha in full."""

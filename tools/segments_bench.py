@@ -1,0 +1,149 @@
+"""Time of decode_latent_segments on many short events at the C3 shape (N = 512, L = 512),
+against the route available without it: one decode_marginals call per event.
+
+S events (--events, default 2000) with geometric lengths of mean 25 clipped to [3, 200]
+(fixed seed) are cut from bench.synth's seeded recording.  Reported: the wall time of one
+decode_latent_segments call (best of --calls after --warmup), its device time by section
+(KernelTimer), the wall time of a loop of decode_marginals calls over the first 50 events
+scaled to S, and the ratio of the two.  Prints one JSON line and writes it to
+profiles/segments_bench_c3.json (--json).
+
+--crossover: one segment of 256, 1024, 4096, 16384 and 65536 rows through both routes of
+decode_latent_segments -- one wave (ScanConfig.segment_wave_max above the length) and the
+chunk-parallel scans (segment_wave_max = 1) -- and the largest power of two at which the
+one-wave route is not slower (wall time, best of --calls); written to
+profiles/segments_crossover_c3.json.  ScanConfig.segment_wave_max's default cites it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import poor_man_gplvm_amd as P  # noqa: E402
+from poor_man_gplvm_amd.engine import KernelTimer, ScanConfig  # noqa: E402
+
+N, L = 512, 512
+CROSSOVER_LENGTHS = (256, 1024, 4096, 16384, 65536)
+
+
+def event_intervals(S, T, seed=0):
+    """(S, 2) [start, stop) rows: geometric lengths (mean 25) clipped to [3, 200], uniform starts."""
+    rng = np.random.default_rng(seed)
+    lens = np.clip(rng.geometric(1.0 / 25.0, size=S), 3, 200)
+    start = rng.integers(0, T - lens + 1)
+    return np.stack([start, start + lens], 1).astype(np.int64)
+
+
+def model(timer=None, **scan):
+    m = P.PoissonGPLVMJump1D(N, n_latent_bin=L, tuning_lengthscale=10., movement_variance=1.,
+                             scan_config=ScanConfig(**scan))
+    if timer is not None:       # every engine the decode builds reports to the timer
+        make = m._decode_engine
+
+        def with_timer(*a, **k):
+            eng = make(*a, **k)
+            eng.timer = timer
+            return eng
+        m._decode_engine = with_timer
+    return m
+
+
+def wall_ms(fn, calls, warmup):
+    for _ in range(warmup):
+        fn()
+    best = float('inf')
+    for _ in range(calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        best = min(best, 1e3 * (time.perf_counter() - t0))
+    return best
+
+
+def sections_ms(timer):
+    return {k: round(n * ms, 4) for k, (n, ms) in sorted(timer.summary().items())}
+
+
+def save(path, rec):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def run_events(args, y, tun):
+    seg = event_intervals(args.events, y.shape[0])
+    m = model()
+    one = wall_ms(lambda: m.decode_latent_segments(y, seg, tuning=tun), args.calls, args.warmup)
+    timer = KernelTimer()
+    mt = model(timer)
+    mt.decode_latent_segments(y, seg, tuning=tun)
+    kern = sections_ms(timer)
+    n_loop = min(50, len(seg))
+
+    def loop():
+        for a, b in seg[:n_loop]:
+            m.decode_marginals(y[a:b], tuning=tun)
+    per_event = wall_ms(loop, max(1, args.calls // 2), 1) / n_loop
+    loop_ms = per_event * len(seg)
+    return {"shape": "c3", "N": N, "L": L, "events": int(len(seg)), "rows": int((seg[:, 1] - seg[:, 0]).sum()),
+            "mean_length": round(float((seg[:, 1] - seg[:, 0]).mean()), 2),
+            "decode_latent_segments_wall_ms": round(one, 3), "decode_latent_segments_kernel_ms": kern,
+            "decode_marginals_per_event_wall_ms": round(per_event, 3), "loop_events_timed": n_loop,
+            "decode_marginals_loop_wall_ms_scaled": round(loop_ms, 1),
+            "loop_over_one_call": round(loop_ms / one, 1)}
+
+
+def run_crossover(args, y, tun):
+    table, best = [], 0
+    for n in CROSSOVER_LENGTHS:
+        seg = np.array([[0, n]])
+        row = {"length": n}
+        for name, wave_max in (("one_wave", 1 << 30), ("chunk_parallel", 1)):
+            timer = KernelTimer()
+            m = model(timer, segment_wave_max=wave_max)
+            row[name + "_wall_ms"] = round(wall_ms(lambda: m.decode_latent_segments(y, seg, tuning=tun), args.calls,
+                                                   args.warmup), 3)
+            timer.reset()
+            m.decode_latent_segments(y, seg, tuning=tun)
+            row[name + "_kernel_ms"] = sections_ms(timer)
+        table.append(row)
+    for row in table:           # the largest length up to which one wave was never slower
+        if row["one_wave_wall_ms"] <= row["chunk_parallel_wall_ms"]:
+            best = row["length"]
+        else:
+            break
+    return {"shape": "c3", "N": N, "L": L, "table": table, "one_wave_not_slower_up_to": best,
+            "rule": "wall time of one decode_latent_segments call, best of --calls; lengths are powers of two"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--events", type=int, default=2000)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    T = bench.CONFIGS["c3"][1]
+    y, B, W0, _ = bench.synth(N, T, L)
+    tun = np.logaddexp(B.astype(np.float64) @ W0.astype(np.float64), 0.0)
+    if args.crossover:
+        rec = run_crossover(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_crossover_c3.json")
+    else:
+        rec = run_events(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_bench_c3.json")
+    print(json.dumps(rec), flush=True)
+    save(path, rec)
+
+
+if __name__ == "__main__":
+    main()
