@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PMG_ABI_VERSION 3
+#define PMG_ABI_VERSION 4
 
 #define PMG_OK 0
 #define PMG_EINVAL (-1)       /* bad shape / argument */
@@ -394,6 +394,38 @@ int pmg_segment_smoother(const float* delta, const float* phi, const double* m, 
                          const pmg_transition* tr, double likelihood_scale,
                          float* alpha, float* gamma, float* P, double* logc, double* logz,
                          void* stream);
+
+/* ------------------------------------------------------------------ */
+/* Most likely (dynamics, latent) paths of many short, independent chains  */
+/* in one call (ragged MAP decoding): pmg_viterbi_decode's recurrence,     */
+/* back-trace and f64 score once per segment of a CSR of rows, one wave    */
+/* per segment, banded transitions only.                                   */
+/*   delta, phi, rblk: the emission of T gathered rows, exactly as         */
+/*            pmg_viterbi_decode takes them with R = 1;                    */
+/*   seg_off, order: as pmg_segment_smoother takes them (the kernels clamp */
+/*            each segment to 0 <= a <= b <= T; `order` changes scheduling */
+/*            only, entries outside 0 .. S-1 are skipped);                 */
+/*   log_pi0  (2, L) DEVICE f64: the log prior of every segment's first    */
+/*            row, as in pmg_viterbi_decode.                               */
+/* outputs: path_d, path_l (T) int32, row t of segment s at seg_off[s] + t; */
+/*          log_joint (S) f64 = log p(path, y) of each segment; an empty   */
+/*          segment (a >= b) only gets log_joint[s] = 0.                   */
+/* Contract: a segment's three outputs equal those of pmg_viterbi_decode   */
+/* (R = 1) on that segment's rows alone, bit for bit (the same arithmetic  */
+/* in the same order, the score's summation order counted from the         */
+/* segment's first row).  They do not depend on which other segments are   */
+/* in the call, on their order, or on `order`.  Rows that no segment owns  */
+/* are not written.  (Segments that overlap after clamping race on their   */
+/* shared rows, within the buffers.)                                       */
+/* Workspace: ~T*Lpad + 12*T bytes plus 8 per segment, Lpad =              */
+/* pmg_fwdbwd_lpad(L); no zero-fill needed.  The size is 0 where           */
+/* unsupported (L > 1024, T <= 0, S < 1); PMG_EUNSUPPORTED for L > 1024.   */
+size_t pmg_segment_viterbi_workspace_size(int64_t T, int32_t L, int32_t S);
+int pmg_segment_viterbi(const float* delta, const float* phi, const double* rblk, int64_t T,
+                        const int64_t* seg_off, int32_t S, const int32_t* order,
+                        const pmg_transition* tr, const double* log_pi0, double likelihood_scale,
+                        int32_t* path_d, int32_t* path_l, double* log_joint,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ */
 /* Dense log-domain scans: any continuous kernel (custom_transition_kernel,  */

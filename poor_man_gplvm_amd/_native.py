@@ -37,7 +37,7 @@ PHASE_NO_ALPHA = 16
 PHASE_P_BF16X3 = 32
 # phase-1 calls: each main-pass chain on two waves where compiled (PMG_PHASE_TWO_WAVES)
 PHASE_TWO_WAVES = 64
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 def phase_segments(S: int) -> int:
@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "pmg_host_alloc", "pmg_host_free", "pmg_copy_d2h",
     "pmg_joint_log_workspace_size", "pmg_joint_log_accumulate_ws", "pmg_posterior_outputs",
     "pmg_viterbi_workspace_size", "pmg_viterbi_decode", "pmg_segment_smoother",
+    "pmg_segment_viterbi_workspace_size", "pmg_segment_viterbi",
 )
 
 
@@ -194,6 +195,9 @@ _SIGS = {
                            _I32),
     "pmg_segment_smoother": ([_P, _P, _P, _I64, _P, _I32, _P, ctypes.POINTER(Transition), _D, _P, _P, _P, _P, _P, _P],
                              _I32),
+    "pmg_segment_viterbi_workspace_size": ([_I64, _I32, _I32], _SZ),
+    "pmg_segment_viterbi": ([_P, _P, _P, _I64, _P, _I32, _P, ctypes.POINTER(Transition), _P, _D, _P, _P, _P, _P, _SZ,
+                             _P], _I32),
 }
 
 _lib = None

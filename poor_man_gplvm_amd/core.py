@@ -547,6 +547,48 @@ class PoissonGPLVMJump1D:
                 'log_likelihood_all': h_ll,
                 'log_marginal_final': h_lz}
 
+    def decode_latent_segments_viterbi(self, y, segments=None, tuning=None, hyperparam={}, ma_neuron=None,
+                                       ma_latent=None, likelihood_scale=1.):
+        """The jointly most likely (dynamics, latent) path of many independent events (ripple
+        or replay candidates, trials, epochs) in one call: what decode_latent_viterbi gives on
+        each event alone, bit for bit (path and log_joint_map), whatever other events are in
+        the call and in whatever order.  Each event is a chain of its own, started from the
+        filters' own prior, with no state carried across the gaps.
+
+        Inputs as decode_latent_segments: y (T, N) with segments (S, 2) integer [start, stop)
+        row intervals (unsorted and overlapping ones are fine), or a list of (T_s, N) arrays
+        with segments=None.  The rows are gathered into one compact array in the order given;
+        one emission serves all events and one wave per event walks it (pmg_segment_viterbi),
+        however long the event: decode_latent_viterbi is one wave per sequence too.
+
+        Returns {'segment_offsets': (S + 1,) int64, 'map_dynamics': (Ttot,) int32,
+        'map_latent': (Ttot,) int32, 'log_joint_map': (S,) float64}; event s is rows
+        segment_offsets[s]:segment_offsets[s + 1].  The latent-only models omit map_dynamics
+        (their MAP path runs on the band, as in decode_latent_viterbi).  A transition that
+        needs the dense scans (custom kernel, n_latent_bin > 1024, band > 32) raises
+        NotImplementedError, and bad intervals ValueError, before any device work."""
+        if _is_tsd(y):
+            y = y.d
+        hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
+        tr = self._map_transition(hp, 'decode_latent_segments_viterbi')   # host-only: raises for a dense transition
+        if ma_neuron is None:
+            ma_neuron = self.ma_neuron_default
+        yc, off, ma = gather_segments(y, segments, ma_neuron)
+        if tuning is None:
+            tuning = self.tuning
+        if ma_latent is None:
+            ma_latent = self.ma_latent_default
+        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
+        if eng.dense:       # the latent-only models' smoother transition; the MAP path takes the band
+            eng.set_transition(tr)
+        eng.emission(likelihood_scale)
+        pd, pl, lj = eng.segment_viterbi(likelihood_scale, torch.as_tensor(off, device=eng.dev),
+                                         torch.as_tensor(segment_order(off), device=eng.dev))
+        eng.check_status()
+        res = {'segment_offsets': off}
+        res.update(self._viterbi_result(_np(pd), _np(pl), _np(lj)))
+        return res
+
     def _map_transition(self, hyperparam, what='decode_latent_viterbi'):
         """The banded transition decode_latent_viterbi maximises over (and
         decode_latent_segments smooths with), from host arithmetic alone; NotImplementedError

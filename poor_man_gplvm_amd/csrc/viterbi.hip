@@ -9,7 +9,8 @@
 //   v1       = max_i a[1][i] - log L                      (one scalar and arg-max per step)
 //   delta_'[d'][j] = v_d'[j] + s*delta[t,j] + phi[t,j/32]
 //
-// MI355X design:
+// MI355X design (the per-chain device code is in viterbi_kernels.h, shared with the
+// ragged kernel set of segment_viterbi.hip):
 //   * one wave per sequence, the filters' lane layout (lane l owns latents lJ .. lJ+J-1,
 //     Lpad = 64 J); the band maximum takes its halo from the neighbouring lanes through
 //     wave_shr:1 / wave_shl:1 DPP moves (the lanes past either end read -inf), as
@@ -29,416 +30,46 @@
 //   * score: a T-parallel gather of the path's per-step increments in f64 (ll as
 //     rblk + delta, the transition logs from the f32 device values), reduced in a fixed
 //     order.  Nothing of the f32 scan enters it.
-#include <math.h>
-
-#include "fb_kernels.h"
+#include "viterbi_kernels.h"
 
 namespace pmg {
 
-struct VitParams {
-  const float* delta;     // (R T, L)
-  const float* phi;       // (R T, nblk)
-  const double* rblk;     // (R T, nblk)
-  const float* invz;      // (L)
-  const double* log_pi0;  // (2, L)
-  int64_t T;
-  int L, Lpad, nblk, band, R;
-  float lg[kMaxBand + 1];  // log g[k] (-inf beyond the band)
-  float la[4];             // log A00 A01 A10 A11 (-inf allowed)
-  float logL, s;
-  double lg64[kMaxBand + 1];
-  double la64[4];
-  double logL64, s64;
-  uint8_t* bp;    // [R][T][Lpad] back-pointer bytes (row 0 of a sequence is not used)
-  int32_t* jp;    // [R][T] jump back-pointers
-  int32_t* last;  // [R][2] the final (d, l)
-  double* inc;    // [R][T] per-step increments of the path score
-  int32_t* path_d;
-  int32_t* path_l;
-  double* log_joint;
-};
-
-template <int J> constexpr int vit_pf() { return J >= 16 ? 2 : 4; }
-
-template <int J>
-struct VitRow {
-  RowV<J> d;
-  float ph;
-};
-
-template <int J, int VEC>
-__device__ __forceinline__ void vit_load(const VitParams& p, const float* delta, const float* phi, int64_t t, int j0,
-                                         VitRow<J>& r) {
-  bload_row<J, VEC>(delta + t * p.L, p.L, j0, r.d);
-  const __amdgpu_buffer_rsrc_t rs = rsrc_of(phi + t * p.nblk, (uint32_t)p.nblk * 4u);
-  r.ph = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (j0 >> 5) * 4, 0, 0));
-}
-
-// two independent wave maxima (interleaved), each in every lane
-__device__ __forceinline__ void wave_max2(float& a, float& b) {
-  a = fmaxf(a, dppf<0xB1>(a));
-  b = fmaxf(b, dppf<0xB1>(b));
-  a = fmaxf(a, dppf<0x4E>(a));
-  b = fmaxf(b, dppf<0x4E>(b));
-  a = fmaxf(a, dppf<0x141>(a));
-  b = fmaxf(b, dppf<0x141>(b));
-  a = fmaxf(a, dppf<0x140>(a));
-  b = fmaxf(b, dppf<0x140>(b));
-  a = fmaxf(a, dppf<0x142, 0xa>(a));
-  b = fmaxf(b, dppf<0x142, 0xa>(b));
-  a = fmaxf(a, dppf<0x143, 0xc>(a));
-  b = fmaxf(b, dppf<0x143, 0xc>(b));
-  a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));
-  b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), 63));
-}
-
-// the value `x` of the first lane whose `v` equals the wave maximum `m` (lane 0 if none)
-__device__ __forceinline__ int first_at_max(float v, float m, int x) {
-  const unsigned long long mask = __ballot(v == m);
-  const int ls = mask ? (int)__builtin_ctzll(mask) : 0;
-  return __builtin_amdgcn_readlane(x, __builtin_amdgcn_readfirstlane(ls));
-}
-
-// out[j] = max_{k=-WP..WP} (in[j+k] + lg[|k|]) over the whole latent line (-inf halo),
-// code[j] = k + WP of the maximiser with the smallest k (np.argmax's first index);
-// WP (the centre) where every candidate is -inf.
-template <int J, int WP>
-__device__ __forceinline__ void band_max(const VitParams& p, const float in[J], float out[J], int code[J]) {
-  constexpr int NL = (WP + J - 1) / J;  // neighbour lanes on each side
-  constexpr int C = NL * J;             // window index of this lane's first latent
-  const float ninf = -INFINITY;
-  float win[J + 2 * C];
-#pragma unroll
-  for (int i = 0; i < J; ++i) win[C + i] = in[i];
-#pragma unroll
-  for (int k = 1; k <= NL; ++k)
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-      if (k * J - i > WP) win[C - k * J + i] = ninf;
-      else win[C - k * J + i] = wave_shr1_in(win[C - (k - 1) * J + i], ninf);
-    }
-#pragma unroll
-  for (int k = 1; k <= NL; ++k)
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-      if (k * J + i - (J - 1) > WP) win[C + k * J + i] = ninf;
-      else win[C + k * J + i] = wave_shl1_in(win[C + (k - 1) * J + i], ninf);
-    }
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    float best = ninf;
-    int bc = WP;
-#pragma unroll
-    for (int k = -WP; k <= WP; ++k) {
-      const float c = win[C + j + k] + p.lg[k < 0 ? -k : k];
-      const bool gt = c > best;
-      best = gt ? c : best;
-      bc = gt ? (k + WP) : bc;
-    }
-    out[j] = best;
-    code[j] = bc;
-  }
-}
-
-// J back-pointer bytes of one lane, row `row` (Lpad bytes: every lane is in range)
-template <int J>
-__device__ __forceinline__ void store_codes(uint8_t* row, int Lpad, int j0, const uint32_t b[J]) {
-  const __amdgpu_buffer_rsrc_t rs = rsrc_of(row, (uint32_t)Lpad);
-  if constexpr (J == 1) {
-    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)b[0], rs, j0, 0, 0);
-  } else if constexpr (J == 2) {
-    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(b[0] | (b[1] << 8)), rs, j0, 0, 0);
-  } else {
-    uint32_t w[J / 4];
-#pragma unroll
-    for (int i = 0; i < J / 4; ++i) w[i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
-    if constexpr (J == 4) {
-      __builtin_amdgcn_raw_buffer_store_b32(w[0], rs, j0, 0, 0);
-    } else if constexpr (J == 8) {
-      const u32x2 q = {w[0], w[1]};
-      __builtin_amdgcn_raw_buffer_store_b64(q, rs, j0, 0, 0);
-    } else {
-      static_assert(J == 16, "lane layouts: J in {1, 2, 4, 8, 16}");
-      const u32x4 q = {w[0], w[1], w[2], w[3]};
-      __builtin_amdgcn_raw_buffer_store_b128(q, rs, j0, 0, 0);
-    }
-  }
-}
-
-template <int J, int WP, int VEC>
-__device__ __forceinline__ void vit_forward(const VitParams& p, int r) {
-  constexpr int PF = vit_pf<J>();
-  const float ninf = -INFINITY;
-  const int j0 = (int)threadIdx.x * J;
-  const float* delta = p.delta + (int64_t)r * p.T * p.L;
-  const float* phi = p.phi + (int64_t)r * p.T * p.nblk;
-  uint8_t* bp = p.bp + (int64_t)r * p.T * p.Lpad;
-  int32_t* jp = p.jp + (int64_t)r * p.T;
-  const int shift = WP - p.band;   // code of band_max -> i - j + band
-
-  bool ok[J];
-  float linvz[J], d0[J], d1[J];
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    ok[j] = j0 + j < p.L;
-    linvz[j] = ok[j] ? (float)log((double)p.invz[j0 + j]) : ninf;
-  }
-  {  // t = 0: the filter's own prior, centred by its maximum in f64 before it is rounded
-     // to f32 (pi0[0, j] and pi0[1, j] differ by ~1e-8 relative in the interior)
-    VitRow<J> r0;
-    vit_load<J, VEC>(p, delta, phi, 0, j0, r0);
-    double lp0[J], lp1[J];
-    double c0 = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      lp0[j] = ok[j] ? p.log_pi0[j0 + j] : (double)-INFINITY;
-      lp1[j] = ok[j] ? p.log_pi0[p.L + j0 + j] : (double)-INFINITY;
-      c0 = fmax(c0, fmax(lp0[j], lp1[j]));
-    }
-    c0 = wave_max_f64(c0);
-    if (!(c0 > -1.0e300)) c0 = 0.0;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const float em = fmaf(p.s, r0.d[j], r0.ph);
-      d0[j] = ok[j] ? (float)(lp0[j] - c0) + em : ninf;
-      d1[j] = ok[j] ? (float)(lp1[j] - c0) + em : ninf;
-    }
-  }
-  if (p.T > 1) {
-    const int64_t last = p.T - 1;
-    VitRow<J> ring[PF];
-#pragma unroll
-    for (int q = 0; q < PF; ++q) vit_load<J, VEC>(p, delta, phi, 1 + q < last ? 1 + q : last, j0, ring[q]);
-    auto body = [&](int q, int64_t t, bool refill) {
-      float em[J];
-      order_after(ring[q].ph, d0[0]);
-#pragma unroll
-      for (int j = 0; j < J; ++j) em[j] = fmaf(p.s, ring[q].d[j], ring[q].ph);
-      slot_consumed<J>(em);
-      if (refill) vit_load<J, VEC>(p, delta, phi, t + PF < last ? t + PF : last, j0, ring[q]);
-      // dynamics mix; the lane's best jump predecessor (first index on ties)
-      float a0[J];
-      uint32_t b0[J];
-      float m0 = ninf, lv = ninf;
-      int li = j0, lb = 0;
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        const float x = d0[j] + p.la[0], y = d1[j] + p.la[2];
-        const bool by = y > x;
-        a0[j] = by ? y : x;
-        b0[j] = by ? 0x80u : 0u;
-        m0 = fmaxf(m0, a0[j]);
-        const float u = d0[j] + p.la[1], w = d1[j] + p.la[3];
-        const bool bw = w > u;
-        const float a1 = bw ? w : u;
-        const bool gt = a1 > lv;
-        lv = gt ? a1 : lv;
-        li = gt ? j0 + j : li;
-        lb = gt ? (bw ? 1 : 0) : lb;
-      }
-      float M0 = m0, M1 = lv;
-      wave_max2(M0, M1);
-      const int jw = first_at_max(lv, M1, li | (lb << 16));
-      float c = fmaxf(M0, M1);
-      if (!(c > -3.0e38f)) c = 0.f;
-      float ain[J], v0[J];
-      int code[J];
-#pragma unroll
-      for (int j = 0; j < J; ++j) ain[j] = a0[j] + linvz[j];
-      band_max<J, WP>(p, ain, v0, code);
-      const float v1 = (M1 - p.logL) - c;
-      uint32_t bytes[J];
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        d0[j] = ok[j] ? (v0[j] - c) + em[j] : ninf;
-        d1[j] = ok[j] ? v1 + em[j] : ninf;
-        bytes[j] = (uint32_t)(code[j] - shift) | b0[j];
-      }
-      store_codes<J>(bp + t * p.Lpad, p.Lpad, j0, bytes);
-      const __amdgpu_buffer_rsrc_t rs = rsrc_of(jp + t, 4u);
-      __builtin_amdgcn_raw_buffer_store_b32((uint32_t)jw, rs, threadIdx.x == 0 ? 0 : 64, 0, 0);
-    };
-    int64_t tb = 1;
-    for (; tb + PF <= p.T; tb += PF) {
-#pragma unroll
-      for (int q = 0; q < PF; ++q) body(q, tb + q, true);
-    }
-#pragma unroll
-    for (int q = 0; q < PF; ++q)
-      if (tb + q < p.T) body(q, tb + q, false);
-  }
-  // the final state: argmax over the flattened (2, L) scores (first index on ties)
-  float l0 = ninf, l1 = ninf;
-  int i0 = j0, i1 = j0;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const bool g0 = d0[j] > l0, g1 = d1[j] > l1;
-    l0 = g0 ? d0[j] : l0;
-    i0 = g0 ? j0 + j : i0;
-    l1 = g1 ? d1[j] : l1;
-    i1 = g1 ? j0 + j : i1;
-  }
-  float M0 = l0, M1 = l1;
-  wave_max2(M0, M1);
-  const int e0 = first_at_max(l0, M0, i0), e1 = first_at_max(l1, M1, i1);
-  if (threadIdx.x == 0) {
-    const bool jump = M1 > M0;
-    p.last[2 * r] = jump ? 1 : 0;
-    p.last[2 * r + 1] = jump ? e1 : e0;
-  }
-}
-
 template <int J, int WP>
 __global__ void __launch_bounds__(64) k_viterbi_fwd(VitParams p) {
-  const int r = blockIdx.y;
+  const VitSeq ch = {(int)blockIdx.y};
   if constexpr (J % 4 == 0) {
     if ((p.L & 3) == 0) {
-      vit_forward<J, WP, 1>(p, r);
+      vit_forward<J, WP, 1>(p, ch);
       return;
     }
   }
-  vit_forward<J, WP, 0>(p, r);
+  vit_forward<J, WP, 0>(p, ch);
 }
 
-// Back-trace.  A piece is NP = min(64, 16384 / Lpad) consecutive rows (<= 16 KiB, <= 16
-// 16-byte loads per lane); lane s of the wave keeps step s of the piece, so the path
-// leaves in one coalesced store per piece.
-constexpr int kTracePieceBytes = 16384;
 __global__ void __launch_bounds__(64) k_viterbi_trace(VitParams p) {
-  __shared__ __attribute__((aligned(16))) uint8_t rows[kTracePieceBytes];
-  __shared__ int32_t jrow[64];
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const int Lpad = p.Lpad;
-  const int NP = kTracePieceBytes / Lpad < 64 ? kTracePieceBytes / Lpad : 64;
-  const int nv = NP * Lpad / 1024;
-  const int64_t T = p.T;
-  const uint8_t* bp = p.bp + (int64_t)r * T * Lpad;
-  const int32_t* jp = p.jp + (int64_t)r * T;
-  const int64_t end = T * Lpad - 16;   // the last 16-byte group of this sequence's rows
-  const int64_t npiece = (T + NP - 1) / NP;
-  u32x4 regs[16];
-  int32_t jreg = 0;
-  auto load_piece = [&](int64_t pc) {
-    const int64_t base = pc * NP;
-#pragma unroll
-    for (int v = 0; v < 16; ++v)
-      if (v < nv) {
-        int64_t off = base * Lpad + v * 1024 + lane * 16;
-        off = off < end ? off : end;
-        regs[v] = *reinterpret_cast<const u32x4*>(bp + off);
-      }
-    const int64_t tj = base + lane < T ? base + lane : T - 1;
-    jreg = jp[tj];
-  };
-  int d = p.last[2 * r], l = p.last[2 * r + 1];
-  d = __builtin_amdgcn_readfirstlane(d);
-  l = __builtin_amdgcn_readfirstlane(l);
-  load_piece(npiece - 1);
-  for (int64_t pc = npiece - 1; pc >= 0; --pc) {
-    const int64_t base = pc * NP;
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < 16; ++v)
-      if (v < nv) *reinterpret_cast<u32x4*>(rows + v * 1024 + lane * 16) = regs[v];
-    jrow[lane] = jreg;
-    __syncthreads();
-    if (pc > 0) load_piece(pc - 1);
-    const int s_hi = (int)((base + NP < T ? base + NP : T) - base) - 1;
-    int myd = 0, myl = 0;
-    for (int s = s_hi; s >= 0; --s) {
-      myd = lane == s ? d : myd;
-      myl = lane == s ? l : myl;
-      if (base + s == 0) break;
-      if (d == 1) {
-        const int w = __builtin_amdgcn_readfirstlane(jrow[s]);
-        l = w & 0xffff;
-        d = (w >> 16) & 1;
-      } else {
-        const int code = __builtin_amdgcn_readfirstlane((int)rows[s * Lpad + l]);
-        int i = l + (code & 127) - p.band;
-        i = i < 0 ? 0 : (i > p.L - 1 ? p.L - 1 : i);
-        d = __builtin_amdgcn_readfirstlane((int)rows[s * Lpad + i]) >> 7;
-        l = i;
-      }
-      l = l > p.L - 1 ? p.L - 1 : l;
-    }
-    if (lane <= s_hi) {
-      p.path_d[(int64_t)r * T + base + lane] = myd;
-      p.path_l[(int64_t)r * T + base + lane] = myl;
-    }
-  }
+  const VitSeq ch = {(int)blockIdx.x};
+  vit_trace(p, ch);
 }
 
 // per-step increments of log p(x, y) along the path, f64
 __global__ void __launch_bounds__(256) k_viterbi_inc(VitParams p) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= p.T * p.R) return;
-  const int64_t t = idx % p.T;
-  const int d = p.path_d[idx], l = p.path_l[idx];
-  if ((unsigned)d > 1u || (unsigned)l >= (unsigned)p.L) {
-    p.inc[idx] = __longlong_as_double(0x7ff8000000000000ll);
-    return;
-  }
-  const double ll = p.rblk[idx * p.nblk + (l >> 5)] + (double)p.delta[idx * p.L + l];
-  double v = p.s64 * ll;
-  if (t == 0) {
-    v += p.log_pi0[d * p.L + l];
-  } else {
-    const int dp = p.path_d[idx - 1] & 1;
-    int lp = p.path_l[idx - 1];
-    lp = lp < 0 ? 0 : (lp > p.L - 1 ? p.L - 1 : lp);
-    v += p.la64[dp * 2 + d];
-    if (d == 0) {
-      const int k = l > lp ? l - lp : lp - l;
-      v += (k <= p.band ? p.lg64[k] : (double)-INFINITY) + log((double)p.invz[lp]);
-    } else {
-      v -= p.logL64;
-    }
-  }
-  p.inc[idx] = v;
+  vit_increment(p, idx, idx % p.T == 0);
 }
 
 // log_joint[r] = sum_t inc[r][t]: thread i adds steps i, i + 256, ... in order, then a
 // fixed tree over the 256 partial sums (the same order whatever R is)
 __global__ void __launch_bounds__(256) k_viterbi_sum(VitParams p) {
   __shared__ double part[256];
-  const int r = blockIdx.x, tid = threadIdx.x;
-  const double* inc = p.inc + (int64_t)r * p.T;
-  double a = 0.0;
-  for (int64_t t = tid; t < p.T; t += 256) a += inc[t];
-  part[tid] = a;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (tid < h) part[tid] += part[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) p.log_joint[r] = part[0];
+  const int r = blockIdx.x;
+  const double v = vit_sum(p.inc + (int64_t)r * p.T, p.T, part);
+  if (threadIdx.x == 0) p.log_joint[r] = v;
 }
 
 // ---------------------------------------------------------------------------
 // host dispatch
 // ---------------------------------------------------------------------------
-static int vit_J(int L) {
-  if (L <= 0) return -1;
-  if (L <= 64) return 1;
-  if (L <= 128) return 2;
-  if (L <= 256) return 4;
-  if (L <= 512) return 8;
-  if (L <= 1024) return 16;
-  return -1;
-}
-// band = ceil(8.31 mv): 5 (mv 0.5), 9 (mv 1, the default), 17 (mv 2); wider ones share 32
-static int vit_WP(int band) {
-  if (band <= 5) return 5;
-  if (band <= 9) return 9;
-  if (band <= 17) return 17;
-  return 32;
-}
-
-#define PMG_VIT_ALL(X)                                                                      \
-  X(1, 5) X(1, 9) X(1, 17) X(1, 32) X(2, 5) X(2, 9) X(2, 17) X(2, 32) X(4, 5) X(4, 9)       \
-  X(4, 17) X(4, 32) X(8, 5) X(8, 9) X(8, 17) X(8, 32) X(16, 5) X(16, 9) X(16, 17) X(16, 32)
-
 typedef void (*vit_kernel_t)(VitParams);
 static vit_kernel_t vit_kernel(int J, int WP) {
 #define PMG_VIT_CASE(JJ, WW) \
@@ -512,30 +143,13 @@ int pmg_viterbi_decode(const float* delta, const float* phi, const double* rblk,
   PMG_REQUIRE((cells + 255) / 256 <= 0x7fffffffll, "pmg_viterbi_decode: T * R = %lld too large", (long long)cells);
 
   VitParams p;
-  memset(&p, 0, sizeof(p));
+  vit_fill_params(p, tr, J, likelihood_scale);
   p.delta = delta;
   p.phi = phi;
   p.rblk = rblk;
-  p.invz = tr->invz;
   p.log_pi0 = log_pi0;
   p.T = T;
-  p.L = tr->L;
-  p.Lpad = 64 * J;
-  p.nblk = (int)(round_up(tr->L, 32) / 32);
-  p.band = tr->band;
   p.R = R;
-  for (int k = 0; k <= kMaxBand; ++k) {
-    p.lg64[k] = (k <= tr->band && tr->g[k] > 0.f) ? log((double)tr->g[k]) : -INFINITY;
-    p.lg[k] = (float)p.lg64[k];
-  }
-  for (int k = 0; k < 4; ++k) {
-    p.la64[k] = tr->A[k] > 0.f ? log((double)tr->A[k]) : -INFINITY;
-    p.la[k] = (float)p.la64[k];
-  }
-  p.logL64 = log((double)tr->L);
-  p.logL = (float)p.logL64;
-  p.s64 = likelihood_scale;
-  p.s = (float)likelihood_scale;
   const VitWork w = carve_vit(workspace, T, p.Lpad, R);
   p.bp = w.bp;
   p.jp = w.jp;

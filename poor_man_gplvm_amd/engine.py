@@ -929,6 +929,38 @@ class DeviceEM:
         self.alpha_bits = 0
         return alpha, logc, logz
 
+    def segment_viterbi(self, likelihood_scale, seg_off, order=None):
+        """Most likely (dynamics, latent) path of every independent segment of the rows in
+        one call (pmg_segment_viterbi: one wave per segment), after emission() with the same
+        likelihood_scale.  seg_off, order: as segment_smoother takes them.  Returns device
+        tensors path_d, path_l (T,) int32 -- rows that no segment owns are left unset -- and
+        log_joint (S,) float64; each segment's outputs equal viterbi() on its rows alone bit
+        for bit."""
+        if self.dense or self._tr_c is None:
+            raise NotImplementedError("segment_viterbi needs a banded transition (set_transition with a "
+                                      "BandedTransition)")
+        T = self.T
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
+            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
+        S = seg_off.numel() - 1
+        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
+            raise ValueError(f"order must be a ({S},) int32 device tensor")
+        need = int(self.lib.pmg_segment_viterbi_workspace_size(T, self.L, S))
+        if need == 0:
+            raise nat.NativeError(f"pmg_segment_viterbi_workspace_size(T={T}, L={self.L}, S={S}) returned 0")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        log_pi0 = torch.as_tensor(viterbi_log_pi0(self._tr), device=self.dev)
+        path_d = torch.empty(T, dtype=torch.int32, device=self.dev)
+        path_l = torch.empty(T, dtype=torch.int32, device=self.dev)
+        lj = torch.empty(S, dtype=torch.float64, device=self.dev)
+        with self._t('segment_viterbi'):
+            nat.check(self.lib.pmg_segment_viterbi(nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.rblk), T,
+                                                   nat.ptr(seg_off), S, nat.ptr(order), ctypes.byref(self._tr_c),
+                                                   nat.ptr(log_pi0), float(likelihood_scale), nat.ptr(path_d),
+                                                   nat.ptr(path_l), nat.ptr(lj), nat.ptr(ws), ws.numel(),
+                                                   nat.stream_handle()), "pmg_segment_viterbi")
+        return path_d, path_l, lj
+
     def e_step(self, likelihood_scale, logz_out, gamma=None, rho=None, log_gamma=None, keep_alpha=None):
         """keep_alpha (default: whenever a posterior output is requested): write alpha in full."""
         if keep_alpha is None:

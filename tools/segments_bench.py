@@ -12,7 +12,12 @@ profiles/segments_bench_c3.json (--json).
 decode_latent_segments -- one wave (ScanConfig.segment_wave_max above the length) and the
 chunk-parallel scans (segment_wave_max = 1) -- and the largest power of two at which the
 one-wave route is not slower (wall time, best of --calls); written to
-profiles/segments_crossover_c3.json.  ScanConfig.segment_wave_max's default cites it."""
+profiles/segments_crossover_c3.json.  ScanConfig.segment_wave_max's default cites it.
+
+--viterbi: the same event set through decode_latent_segments_viterbi (one call; wall time,
+device time by section) against a loop of decode_latent_viterbi calls over the first 50
+events scaled to S; written to profiles/segments_viterbi_bench_c3.json.  The loop is the
+baseline: no ratio is fixed."""
 import argparse
 import json
 import os
@@ -101,6 +106,37 @@ def run_events(args, y, tun):
             "loop_over_one_call": round(loop_ms / one, 1)}
 
 
+def run_viterbi(args, y, tun):
+    seg = event_intervals(args.events, y.shape[0])
+    m = model()
+    one = wall_ms(lambda: m.decode_latent_segments_viterbi(y, seg, tuning=tun), args.calls, args.warmup)
+    timer = KernelTimer()
+    mt = model(timer)
+    res = mt.decode_latent_segments_viterbi(y, seg, tuning=tun)
+    kern = sections_ms(timer)
+    n_loop = min(50, len(seg))
+    singles = []
+
+    def loop():
+        singles[:] = [m.decode_latent_viterbi(y[a:b], tuning=tun) for a, b in seg[:n_loop]]
+    per_event = wall_ms(loop, max(1, args.calls // 2), 1) / n_loop
+    loop_ms = per_event * len(seg)
+    off = res['segment_offsets']
+    same = all(np.array_equal(r['map_latent'], res['map_latent'][off[s]:off[s + 1]]) and
+               np.array_equal(r['map_dynamics'], res['map_dynamics'][off[s]:off[s + 1]]) and
+               r['log_joint_map'] == res['log_joint_map'][s] for s, r in enumerate(singles))
+    return {"shape": "c3", "N": N, "L": L, "events": int(len(seg)), "rows": int((seg[:, 1] - seg[:, 0]).sum()),
+            "mean_length": round(float((seg[:, 1] - seg[:, 0]).mean()), 2),
+            "decode_latent_segments_viterbi_wall_ms": round(one, 3),
+            "decode_latent_segments_viterbi_kernel_ms": kern,
+            "kernel_ms_total": round(sum(kern.values()), 4),
+            "decode_latent_viterbi_per_event_wall_ms": round(per_event, 3), "loop_events_timed": n_loop,
+            "decode_latent_viterbi_loop_wall_ms_scaled": round(loop_ms, 1),
+            "loop_over_one_call": round(loop_ms / one, 1),
+            "loop_events_equal_bit_for_bit": bool(same),
+            "log_joint_map_sum": float(res['log_joint_map'].sum())}
+
+
 def run_crossover(args, y, tun):
     table, best = [], 0
     for n in CROSSOVER_LENGTHS:
@@ -130,6 +166,7 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--viterbi", action="store_true")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     T = bench.CONFIGS["c3"][1]
@@ -138,6 +175,9 @@ def main():
     if args.crossover:
         rec = run_crossover(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_crossover_c3.json")
+    elif args.viterbi:
+        rec = run_viterbi(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_viterbi_bench_c3.json")
     else:
         rec = run_events(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_bench_c3.json")
