@@ -428,6 +428,52 @@ int pmg_segment_viterbi(const float* delta, const float* phi, const double* rblk
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ */
+/* Joint posterior path samples of many short, independent chains in one   */
+/* call: the backward-sampling pass of forward filtering, backward         */
+/* sampling (FFBS).  The reference has no sampler; the recursion is the     */
+/* factorisation of decoder.smooth_one_step's pairwise joint               */
+/* (decoder.py:200-226).  With the flat state index x = d*L + l, per        */
+/* segment [a, b) and sample r, from t = b-1 down to a:                     */
+/*   t = b-1:  w[x] = alpha[t,d,l];                                         */
+/*   t < b-1, (d+, l+) the state drawn at t+1:                              */
+/*     d+ = 0: w[x] = alpha[t,d,l] * A[d,0] * g[|l-l+|] * invz[l] for       */
+/*             |l-l+| <= band, 0 beyond it;                                 */
+/*     d+ = 1: w[x] = alpha[t,d,l] * A[d,1]   (the 1/L cancels);            */
+/*   the draw is the smallest x with cdf[x] > uniforms[r,t] * total, cdf    */
+/*   the inclusive prefix sum of w in x order (f32: the lane's J values in  */
+/*   latent order, a 6-deep scan over the 64 lanes, plus the d = 0 total    */
+/*   for d = 1).  A state whose weight is exactly 0 is never returned       */
+/*   (a masked latent, one beyond the band, a zero of A); where rounding    */
+/*   puts the target at or past the total, the last state of weight > 0     */
+/*   is taken.                                                              */
+/* One wave per (segment, sample), banded transitions only.  The kernel     */
+/* draws no random numbers: the paths are a deterministic function of       */
+/* (alpha, tr, uniforms).                                                   */
+/*   alpha    (T,2,L) f32: the filter posteriors pmg_segment_smoother (or   */
+/*            pmg_forward_filter, per segment) wrote;                       */
+/*   seg_off, order: as pmg_segment_smoother takes them (segments clamped   */
+/*            to 0 <= a <= b <= T on the device; workgroup b takes segment  */
+/*            order[b / R] (NULL: b / R) and sample b % R; `order` changes  */
+/*            scheduling only, entries outside 0 .. S-1 are skipped);       */
+/*   uniforms (R,T) DEVICE f32 in [0, 1): uniforms[r,t] draws row t of      */
+/*            sample r.                                                     */
+/* outputs: path_d, path_l (R,T) int32; rows that no segment owns are not   */
+/*          written.  A sample of a segment depends on that segment's rows  */
+/*          of alpha and of uniforms[r] alone: not on the other segments,   */
+/*          their order, `order`, or R.                                     */
+/*   status   (1) DEVICE int32, sticky: set to 1 when some step's total was */
+/*            0 or not finite (that wave then wrote -1 into the rows it had */
+/*            not drawn yet); never cleared here -- the caller zeroes it    */
+/*            and checks it after the call.                                 */
+/* No workspace.  PMG_EUNSUPPORTED for L > 1024.                            */
+int pmg_segment_sample(const float* alpha, int64_t T,
+                       const int64_t* seg_off, int32_t S, const int32_t* order,
+                       const pmg_transition* tr,
+                       const float* uniforms, int32_t R,
+                       int32_t* path_d, int32_t* path_l, int32_t* status,
+                       void* stream);
+
+/* ------------------------------------------------------------------ */
 /* Dense log-domain scans: any continuous kernel (custom_transition_kernel,  */
 /* gp_kernel.py:30-34 and 61-66; RBF kernels wider than PMG_MAX_BAND; the     */
 /* latent-only model of decoder_latentonly.py:33-224 with A = [[1,0],[1,0]]). */

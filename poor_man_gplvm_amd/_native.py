@@ -72,7 +72,7 @@ EXPORTED_SYMBOLS = (
     "pmg_host_alloc", "pmg_host_free", "pmg_copy_d2h",
     "pmg_joint_log_workspace_size", "pmg_joint_log_accumulate_ws", "pmg_posterior_outputs",
     "pmg_viterbi_workspace_size", "pmg_viterbi_decode", "pmg_segment_smoother",
-    "pmg_segment_viterbi_workspace_size", "pmg_segment_viterbi",
+    "pmg_segment_viterbi_workspace_size", "pmg_segment_viterbi", "pmg_segment_sample",
 )
 
 
@@ -198,6 +198,7 @@ _SIGS = {
     "pmg_segment_viterbi_workspace_size": ([_I64, _I32, _I32], _SZ),
     "pmg_segment_viterbi": ([_P, _P, _P, _I64, _P, _I32, _P, ctypes.POINTER(Transition), _P, _D, _P, _P, _P, _P, _SZ,
                              _P], _I32),
+    "pmg_segment_sample": ([_P, _I64, _P, _I32, _P, ctypes.POINTER(Transition), _P, _I32, _P, _P, _P, _P], _I32),
 }
 
 _lib = None

@@ -510,24 +510,7 @@ class PoissonGPLVMJump1D:
             cp.reserve(key, shape)
         gamma = torch.empty((Ttot, 2, L), dtype=torch.float32, device=dev)
         logz = torch.empty(S, dtype=torch.float64, device=dev)
-        eng.emission(likelihood_scale)
-        short = np.diff(off) <= int(self.scan_config.segment_wave_max)
-        for i0, i1 in _true_runs(short):       # consecutive one-wave segments: one call per run
-            r0, r1 = int(off[i0]), int(off[i1])
-            rel = off[i0:i1 + 1] - r0
-            _, _, lz = eng.segment_smoother(likelihood_scale, torch.as_tensor(rel, device=dev),
-                                            torch.as_tensor(segment_order(rel), device=dev),
-                                            gamma=gamma[r0:r1], rows=(r0, r1))
-            logz[i0:i1] = lz
-        for i in np.flatnonzero(~short):        # the chunk-parallel scans, one segment at a time
-            a, b = int(off[i]), int(off[i + 1])
-            sub = self._decode_engine(yc[a:b], tuning, hp, ma[a:b] if np.ndim(ma) == 2 else ma, ma_latent,
-                                      exact=False)
-            sub.e_step(likelihood_scale, logz[i:i + 1], gamma=gamma[a:b])
-            sub.check_status()
-            eng.alpha[a:b].copy_(sub.alpha)
-            eng.logc[a:b].copy_(sub.logc)
-        eng.check_status()
+        self._segments_scan(eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz, gamma)
         ml = None if ma_latent is None else np.asarray(ma_latent).astype(bool)
         _, plm, pdm = posterior_outputs(gamma, log=False)
         h_lcaus = cp.submit(log_of(eng.alpha), key='lcaus')
@@ -546,6 +529,110 @@ class PoissonGPLVMJump1D:
                 'log_one_step_predictive_marginals_all': h_logc,
                 'log_likelihood_all': h_ll,
                 'log_marginal_final': h_lz}
+
+    def _segments_scan(self, eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz, gamma=None):
+        """The scans of decode_latent_segments / sample_latent_segments over the compact rows
+        of `eng`: emission, then every run of consecutive one-wave segments in one
+        segment_smoother call and every event longer than scan_config.segment_wave_max on the
+        chunk-parallel scans of an engine of its own, spliced into eng.alpha / eng.logc.
+        gamma (Ttot, 2, L) device tensor: filter and smooth; None: the filter alone."""
+        dev = eng.dev
+        eng.emission(likelihood_scale)
+        short = np.diff(off) <= int(self.scan_config.segment_wave_max)
+        for i0, i1 in _true_runs(short):       # consecutive one-wave segments: one call per run
+            r0, r1 = int(off[i0]), int(off[i1])
+            rel = off[i0:i1 + 1] - r0
+            _, _, lz = eng.segment_smoother(likelihood_scale, torch.as_tensor(rel, device=dev),
+                                            torch.as_tensor(segment_order(rel), device=dev),
+                                            gamma=None if gamma is None else gamma[r0:r1], rows=(r0, r1))
+            logz[i0:i1] = lz
+        for i in np.flatnonzero(~short):        # the chunk-parallel scans, one segment at a time
+            a, b = int(off[i]), int(off[i + 1])
+            sub = self._decode_engine(yc[a:b], tuning, hp, ma[a:b] if np.ndim(ma) == 2 else ma, ma_latent,
+                                      exact=False)
+            if gamma is None:
+                sub.emission(likelihood_scale)
+                sub.forward(likelihood_scale, logz[i:i + 1], keep_alpha=True)
+            else:
+                sub.e_step(likelihood_scale, logz[i:i + 1], gamma=gamma[a:b])
+            sub.check_status()
+            eng.alpha[a:b].copy_(sub.alpha)
+            eng.logc[a:b].copy_(sub.logc)
+        eng.check_status()
+
+    def sample_latent_segments(self, y, segments=None, n_samples=100, key=0, uniforms=None, tuning=None,
+                               hyperparam={}, ma_neuron=None, ma_latent=None, likelihood_scale=1.):
+        """Joint posterior samples of the whole (dynamics, latent) path of many independent
+        events (ripple or replay candidates, trials, epochs) in one call: n_samples draws
+        x_{a..b-1} ~ p(x | y) per event by forward filtering, backward sampling (FFBS), for the
+        posterior of path-level quantities (number of jumps, distance travelled, a credible
+        band around the MAP path) that the marginals and the single MAP path do not give.
+        Each event is a chain of its own, started from the filters' own prior, as in
+        decode_latent_segments.  The reference has no sampler; the backward pass is the
+        factorisation of decoder.smooth_one_step's pairwise joint (decoder.py:200-226),
+        p(x_t | x_{t+1}, y) ~ alpha_t[x_t] Trans[x_t, x_{t+1}], over the banded device
+        transition (pmg_segment_sample: one wave per (event, sample)).
+
+        Inputs, gathering, defaults and hyper-parameter overrides as decode_latent_segments;
+        only the filter runs (an event longer than scan_config.segment_wave_max on the
+        chunk-parallel forward).  uniforms: optional (n_samples, Ttot) float32 array or tensor
+        in [0, 1), column = compact row: uniforms[r, t] draws row t of sample r, and the
+        samples are a deterministic function of them.  Without it they come from torch.rand
+        on the device, from a torch.Generator seeded with `key`: the same key and inputs give
+        the same samples.
+
+        Returns {'segment_offsets': (S + 1,) int64, 'sample_dynamics': (n_samples, Ttot) int32,
+        'sample_latent': (n_samples, Ttot) int32, 'log_marginal_final': (S,) float64}; event s
+        of sample r is [r, segment_offsets[s]:segment_offsets[s + 1]].  A transition that needs
+        the dense scans raises NotImplementedError, and bad intervals, n_samples < 1 or bad
+        uniforms ValueError, before any device work."""
+        if _is_tsd(y):
+            y = y.d
+        hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
+        self._map_transition(hp, 'sample_latent_segments')      # host-only: raises for a dense transition
+        R = int(n_samples)
+        if R < 1 or R != n_samples:
+            raise ValueError(f"n_samples must be an integer >= 1, got {n_samples}")
+        if ma_neuron is None:
+            ma_neuron = self.ma_neuron_default
+        yc, off, ma = gather_segments(y, segments, ma_neuron)
+        S, Ttot = len(off) - 1, int(off[-1])
+        if uniforms is not None:
+            uniforms = _checked_uniforms(uniforms, R, Ttot)
+        if tuning is None:
+            tuning = self.tuning
+        if ma_latent is None:
+            ma_latent = self.ma_latent_default
+        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
+        dev = eng.dev
+        if uniforms is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(key))
+            uniforms = torch.rand((R, Ttot), generator=gen, dtype=torch.float32, device=dev)
+        else:
+            uniforms = uniforms.to(dev).contiguous()
+        logz = torch.empty(S, dtype=torch.float64, device=dev)
+        self._segments_scan(eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz)
+        pd, pl = eng.segment_sampler(torch.as_tensor(off, device=dev), uniforms,
+                                     torch.as_tensor(segment_order(off), device=dev))
+        return {'segment_offsets': off, 'sample_dynamics': _np(pd), 'sample_latent': _np(pl),
+                'log_marginal_final': _np(logz)}
+
+    def sample_latent_posterior(self, y, n_samples=100, key=0, uniforms=None, tuning=None, hyperparam={},
+                                ma_neuron=None, ma_latent=None, likelihood_scale=1.):
+        """Joint posterior samples of the (dynamics, latent) path of one sequence y (T, N):
+        sample_latent_segments with the single segment [0, T).  Returns {'sample_dynamics',
+        'sample_latent': (n_samples, T) int32, 'log_marginal_final': float}."""
+        if _is_tsd(y):
+            y = y.d
+        y = np.asarray(y)
+        if y.ndim != 2 or y.shape[0] < 1:
+            raise ValueError(f"y must be a non-empty (n_time, n_neuron) array, got {tuple(y.shape)}")
+        r = self.sample_latent_segments(y, [[0, y.shape[0]]], n_samples=n_samples, key=key, uniforms=uniforms,
+                                        tuning=tuning, hyperparam=hyperparam, ma_neuron=ma_neuron,
+                                        ma_latent=ma_latent, likelihood_scale=likelihood_scale)
+        return {'sample_dynamics': r['sample_dynamics'], 'sample_latent': r['sample_latent'],
+                'log_marginal_final': float(r['log_marginal_final'][0])}
 
     def decode_latent_segments_viterbi(self, y, segments=None, tuning=None, hyperparam={}, ma_neuron=None,
                                        ma_latent=None, likelihood_scale=1.):
@@ -946,6 +1033,20 @@ def segment_order(offsets):
     workgroup order of pmg_segment_smoother."""
     lens = np.diff(np.asarray(offsets, np.int64))
     return np.argsort(-lens, kind='stable').astype(np.int32)
+
+
+def _checked_uniforms(uniforms, n_samples, n_rows):
+    """sample_latent_segments' uniforms as a float32 torch tensor (on whatever device they
+    came on): ValueError unless (n_samples, n_rows) with every value in [0, 1)."""
+    u = uniforms if isinstance(uniforms, torch.Tensor) else torch.tensor(np.asarray(uniforms))
+    if tuple(u.shape) != (n_samples, n_rows):
+        raise ValueError(f"uniforms must be (n_samples, n_rows) = {(n_samples, n_rows)}, got {tuple(u.shape)}")
+    if not u.is_floating_point():
+        raise ValueError(f"uniforms must be floating point, got {u.dtype}")
+    u = u.to(torch.float32)     # after rounding: a float64 just below 1 becomes 1
+    if not bool(((u >= 0) & (u < 1)).all()):
+        raise ValueError("uniforms must lie in [0, 1)")
+    return u
 
 
 def _true_runs(mask):
@@ -1499,6 +1600,12 @@ class PoissonGPLVM1D(PoissonGPLVMJump1D):
         raise NotImplementedError(f"{type(self).__name__}.decode_latent_segments: the latent-only models need the "
                                   "dense log-domain scans, which the segment smoother does not run; call "
                                   "decode_latent once per segment")
+
+    def sample_latent_segments(self, y, segments=None, **kwargs):
+        """Not available, for the reason decode_latent_segments gives: the sampler draws from
+        the banded linear-space filter's posteriors."""
+        raise NotImplementedError(f"{type(self).__name__}.sample_latent_segments: the latent-only models need the "
+                                  "dense log-domain scans, whose filter the path sampler does not read")
 
     def _dynamics_decode_args(self, hyperparam):
         hp = dict(hyperparam)

@@ -961,6 +961,42 @@ class DeviceEM:
                                                    nat.stream_handle()), "pmg_segment_viterbi")
         return path_d, path_l, lj
 
+    def segment_sampler(self, seg_off, uniforms, order=None):
+        """Joint posterior path samples of every independent segment of the rows in one call
+        (pmg_segment_sample: one wave per (segment, sample), backward sampling over the filter
+        posteriors), after a forward pass that left self.alpha in full for those rows
+        (segment_smoother, or forward with keep_alpha).  seg_off, order: as segment_smoother
+        takes them; uniforms (R, T) float32 device tensor in [0, 1), uniforms[r, t] drawing row
+        t of sample r (the kernel makes no random numbers).  Returns device tensors path_d,
+        path_l (R, T) int32, -1 in rows that no segment owns.  Raises NativeError when a
+        step's weights summed to 0 or to a non-finite value (the device status word; the read
+        syncs)."""
+        if self.dense or self._tr_c is None:
+            raise NotImplementedError("segment_sampler needs a banded transition (set_transition with a "
+                                      "BandedTransition)")
+        T = self.T
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
+            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
+        S = seg_off.numel() - 1
+        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
+            raise ValueError(f"order must be a ({S},) int32 device tensor")
+        if (not isinstance(uniforms, torch.Tensor) or uniforms.dtype != torch.float32 or uniforms.dim() != 2
+                or uniforms.shape[0] < 1 or uniforms.shape[1] != T):
+            raise ValueError(f"uniforms must be a (n_samples >= 1, {T}) float32 device tensor")
+        if self.alpha_bits & nat.PHASE_NO_JUMP_ROWS:
+            raise nat.NativeError("segment_sampler needs alpha in full (forward with keep_alpha=True)")
+        R = int(uniforms.shape[0])
+        path_d = torch.full((R, T), -1, dtype=torch.int32, device=self.dev)
+        path_l = torch.full((R, T), -1, dtype=torch.int32, device=self.dev)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        with self._t('segment_sampler'):
+            nat.check(self.lib.pmg_segment_sample(nat.ptr(self.alpha), T, nat.ptr(seg_off), S, nat.ptr(order),
+                                                  ctypes.byref(self._tr_c), nat.ptr(uniforms), R, nat.ptr(path_d),
+                                                  nat.ptr(path_l), nat.ptr(status), nat.stream_handle()),
+                      "pmg_segment_sample")
+        sample_status_check(int(status.item()))
+        return path_d, path_l
+
     def e_step(self, likelihood_scale, logz_out, gamma=None, rho=None, log_gamma=None, keep_alpha=None):
         """keep_alpha (default: whenever a posterior output is requested): write alpha in full."""
         if keep_alpha is None:
@@ -1092,6 +1128,14 @@ def _check_emission_flag(flag):
     if bad:
         raise nat.NativeError("pmg_emission_poisson: |log(tuning*dt)| >= 60 somewhere -- outside the exact "
                               "int8-digit range (the emission of that E-step is invalid)")
+
+
+def sample_status_check(word):
+    """Raise for a set status word of pmg_segment_sample (host value)."""
+    if int(word) != 0:
+        raise nat.NativeError("pmg_segment_sample: the weights of some step summed to 0 or to a non-finite value "
+                              "(no state to draw: the filter posteriors alpha are invalid there); the rest of "
+                              "that path holds -1")
 
 
 def log_of(x: torch.Tensor) -> torch.Tensor:

@@ -17,7 +17,15 @@ profiles/segments_crossover_c3.json.  ScanConfig.segment_wave_max's default cite
 --viterbi: the same event set through decode_latent_segments_viterbi (one call; wall time,
 device time by section) against a loop of decode_latent_viterbi calls over the first 50
 events scaled to S; written to profiles/segments_viterbi_bench_c3.json.  The loop is the
-baseline: no ratio is fixed."""
+baseline: no ratio is fixed.
+
+--sample R: the same event set through sample_latent_segments with R samples per event (one
+call; wall time, device time by section, the sampler kernel's share) next to
+decode_latent_segments on the same events in the same process, the yardstick: the smoother
+pays a backward pass and 2 L floats per row, the sampler R backward draws.  --parent-json: a
+record that the parent commit's tools/segments_bench.py wrote on the same machine, kept
+under "parent_commit".  Written to profiles/segments_sample_bench_c3.json.  No time is
+fixed: the ratio is reported as found."""
 import argparse
 import json
 import os
@@ -137,6 +145,38 @@ def run_viterbi(args, y, tun):
             "log_joint_map_sum": float(res['log_joint_map'].sum())}
 
 
+def run_sample(args, y, tun):
+    seg = event_intervals(args.events, y.shape[0])
+    n = int(args.sample)
+    m = model()
+    one = wall_ms(lambda: m.sample_latent_segments(y, seg, n_samples=n, key=0, tuning=tun), args.calls, args.warmup)
+    timer = KernelTimer()
+    mt = model(timer)
+    res = mt.sample_latent_segments(y, seg, n_samples=n, key=0, tuning=tun)
+    kern = sections_ms(timer)
+    smooth = wall_ms(lambda: m.decode_latent_segments(y, seg, tuning=tun), args.calls, args.warmup)
+    timer.reset()
+    mt.decode_latent_segments(y, seg, tuning=tun)
+    kern_smooth = sections_ms(timer)
+    rows = int((seg[:, 1] - seg[:, 0]).sum())
+    pd, pl = res['sample_dynamics'], res['sample_latent']
+    rec = {"shape": "c3", "N": N, "L": L, "events": int(len(seg)), "rows": rows, "n_samples": n,
+           "mean_length": round(float((seg[:, 1] - seg[:, 0]).mean()), 2),
+           "sample_latent_segments_wall_ms": round(one, 3), "sample_latent_segments_kernel_ms": kern,
+           "kernel_ms_total": round(sum(kern.values()), 4),
+           "segment_sampler_ns_per_drawn_state": round(1e6 * kern.get("segment_sampler", 0.0) / (rows * n), 4),
+           "decode_latent_segments_wall_ms": round(smooth, 3), "decode_latent_segments_kernel_ms": kern_smooth,
+           "decode_latent_segments_kernel_ms_total": round(sum(kern_smooth.values()), 4),
+           "sample_over_decode_wall": round(one / smooth, 3),
+           "sample_over_decode_kernel": round(sum(kern.values()) / sum(kern_smooth.values()), 3),
+           "all_states_drawn": bool(pd.min() >= 0 and pl.min() >= 0),
+           "mean_jump_fraction": round(float((pd == 1).mean()), 6)}
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            rec["parent_commit"] = json.load(f)
+    return rec
+
+
 def run_crossover(args, y, tun):
     table, best = [], 0
     for n in CROSSOVER_LENGTHS:
@@ -167,6 +207,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--crossover", action="store_true")
     ap.add_argument("--viterbi", action="store_true")
+    ap.add_argument("--sample", type=int, default=0, metavar="R")
+    ap.add_argument("--parent-json", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     T = bench.CONFIGS["c3"][1]
@@ -175,6 +217,9 @@ def main():
     if args.crossover:
         rec = run_crossover(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_crossover_c3.json")
+    elif args.sample:
+        rec = run_sample(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_sample_bench_c3.json")
     elif args.viterbi:
         rec = run_viterbi(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_viterbi_bench_c3.json")
