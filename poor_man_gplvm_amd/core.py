@@ -455,10 +455,7 @@ class PoissonGPLVMJump1D:
             if ma_neuron is not None and np.ndim(ma_neuron) != 1:
                 raise ValueError("batched sequences take a 1-D ma_neuron")
             y = y.reshape(y.shape[0] * y.shape[1], y.shape[2])
-        eng = self._decode_engine(y, tuning, hp, ma_neuron, ma_latent, exact=False)
-        if eng.dense:       # the latent-only models' smoother transition; the MAP path takes the band
-            eng.set_transition(tr)
-        eng.emission(likelihood_scale)
+        eng = self._map_engine(y, tuning, hp, ma_neuron, ma_latent, tr, likelihood_scale)
         pd, pl, lj = eng.viterbi(likelihood_scale, max(R, 1))
         eng.check_status()
         pd, pl, lj = _np(pd), _np(pl), _np(lj)
@@ -491,17 +488,8 @@ class PoissonGPLVMJump1D:
         The pairwise joint (p_transition_*) is not formed.  A transition that needs the dense
         scans (custom kernel, n_latent_bin > 1024, band > 32) raises NotImplementedError, and
         bad intervals ValueError, before any device work."""
-        if _is_tsd(y):
-            y = y.d
-        hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
-        self._map_transition(hp, 'decode_latent_segments')      # host-only: raises for a dense transition
-        if ma_neuron is None:
-            ma_neuron = self.ma_neuron_default
-        yc, off, ma = gather_segments(y, segments, ma_neuron)
-        if tuning is None:
-            tuning = self.tuning
-        if ma_latent is None:
-            ma_latent = self.ma_latent_default
+        hp, _, yc, off, ma, tuning, ma_latent = self._segments_prologue(
+            y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'decode_latent_segments')
         S, Ttot, L = len(off) - 1, int(off[-1]), self.n_latent_bin
         eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
         dev = eng.dev
@@ -586,23 +574,14 @@ class PoissonGPLVMJump1D:
         of sample r is [r, segment_offsets[s]:segment_offsets[s + 1]].  A transition that needs
         the dense scans raises NotImplementedError, and bad intervals, n_samples < 1 or bad
         uniforms ValueError, before any device work."""
-        if _is_tsd(y):
-            y = y.d
-        hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
-        self._map_transition(hp, 'sample_latent_segments')      # host-only: raises for a dense transition
-        R = int(n_samples)
-        if R < 1 or R != n_samples:
-            raise ValueError(f"n_samples must be an integer >= 1, got {n_samples}")
-        if ma_neuron is None:
-            ma_neuron = self.ma_neuron_default
-        yc, off, ma = gather_segments(y, segments, ma_neuron)
-        S, Ttot = len(off) - 1, int(off[-1])
+        def check_n_samples():
+            if int(n_samples) < 1 or int(n_samples) != n_samples:
+                raise ValueError(f"n_samples must be an integer >= 1, got {n_samples}")
+        hp, _, yc, off, ma, tuning, ma_latent = self._segments_prologue(
+            y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'sample_latent_segments', check_n_samples)
+        R, S, Ttot = int(n_samples), len(off) - 1, int(off[-1])
         if uniforms is not None:
             uniforms = _checked_uniforms(uniforms, R, Ttot)
-        if tuning is None:
-            tuning = self.tuning
-        if ma_latent is None:
-            ma_latent = self.ma_latent_default
         eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
         dev = eng.dev
         if uniforms is None:
@@ -654,10 +633,28 @@ class PoissonGPLVMJump1D:
         (their MAP path runs on the band, as in decode_latent_viterbi).  A transition that
         needs the dense scans (custom kernel, n_latent_bin > 1024, band > 32) raises
         NotImplementedError, and bad intervals ValueError, before any device work."""
+        hp, tr, yc, off, ma, tuning, ma_latent = self._segments_prologue(
+            y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'decode_latent_segments_viterbi')
+        eng = self._map_engine(yc, tuning, hp, ma, ma_latent, tr, likelihood_scale)
+        pd, pl, lj = eng.segment_viterbi(likelihood_scale, torch.as_tensor(off, device=eng.dev),
+                                         torch.as_tensor(segment_order(off), device=eng.dev))
+        eng.check_status()
+        res = {'segment_offsets': off}
+        res.update(self._viterbi_result(_np(pd), _np(pl), _np(lj)))
+        return res
+
+    def _segments_prologue(self, y, segments, tuning, hyperparam, ma_neuron, ma_latent, what, check=None):
+        """The host half the segment methods open with: the hyper-parameters, the banded
+        transition (NotImplementedError for a dense one), the caller's own argument `check`,
+        the defaults and the gathered rows (ValueError for bad intervals), in that order.  No
+        device work: the caller makes its remaining host checks, then its engine.  Returns
+        (hp, tr, yc, off, ma, tuning, ma_latent)."""
         if _is_tsd(y):
             y = y.d
         hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
-        tr = self._map_transition(hp, 'decode_latent_segments_viterbi')   # host-only: raises for a dense transition
+        tr = self._map_transition(hp, what)
+        if check is not None:
+            check()
         if ma_neuron is None:
             ma_neuron = self.ma_neuron_default
         yc, off, ma = gather_segments(y, segments, ma_neuron)
@@ -665,16 +662,16 @@ class PoissonGPLVMJump1D:
             tuning = self.tuning
         if ma_latent is None:
             ma_latent = self.ma_latent_default
-        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
-        if eng.dense:       # the latent-only models' smoother transition; the MAP path takes the band
+        return hp, tr, yc, off, ma, tuning, ma_latent
+
+    def _map_engine(self, y, tuning, hp, ma_neuron, ma_latent, tr, likelihood_scale):
+        """Engine of a MAP decode with its emission done.  The latent-only models' smoother
+        transition is dense; the MAP path takes the band `tr`."""
+        eng = self._decode_engine(y, tuning, hp, ma_neuron, ma_latent, exact=False)
+        if eng.dense:
             eng.set_transition(tr)
         eng.emission(likelihood_scale)
-        pd, pl, lj = eng.segment_viterbi(likelihood_scale, torch.as_tensor(off, device=eng.dev),
-                                         torch.as_tensor(segment_order(off), device=eng.dev))
-        eng.check_status()
-        res = {'segment_offsets': off}
-        res.update(self._viterbi_result(_np(pd), _np(pl), _np(lj)))
-        return res
+        return eng
 
     def _map_transition(self, hyperparam, what='decode_latent_viterbi'):
         """The banded transition decode_latent_viterbi maximises over (and

@@ -1659,6 +1659,40 @@ static inline int pick_J(int L) {
   if (L <= 1024) return 16;
   return -1;
 }
+// band width of the wave-per-chain kernel sets (segments.hip, viterbi.hip): band =
+// ceil(8.31 mv) is 5 (mv 0.5), 9 (mv 1, the default), 17 (mv 2); wider ones share 32
+static inline int wave_WP(int band) {
+  if (band <= 5) return 5;
+  if (band <= 9) return 9;
+  if (band <= 17) return 17;
+  return 32;
+}
+// their (J, WP) instances
+#define PMG_WAVE_ALL(X)                                                                     \
+  X(1, 5) X(1, 9) X(1, 17) X(1, 32) X(2, 5) X(2, 9) X(2, 17) X(2, 32) X(4, 5) X(4, 9)       \
+  X(4, 17) X(4, 32) X(8, 5) X(8, 9) X(8, 17) X(8, 32) X(16, 5) X(16, 9) X(16, 17) X(16, 32)
+
+// The transition checks of the wave-per-chain entry points, in their order; `fn` opens the
+// error text.  band_below_L: the max-plus kernels also need band < L.  PMG_EUNSUPPORTED
+// (L > 1024) is the last of them: an entry point returns PMG_EINVAL at once and that one
+// after its own argument checks.
+static inline int check_banded_tr(const char* fn, const pmg_transition* tr, bool band_below_L) {
+  PMG_REQUIRE(tr, "%s: tr is null", fn);
+  PMG_REQUIRE(tr->L > 0 && tr->invz, "%s: tr: bad transition (L=%d, invz %s)", fn, tr->L, tr->invz ? "set" : "null");
+  if (band_below_L)
+    PMG_REQUIRE(tr->band >= 0 && tr->band <= kMaxBand && tr->band < tr->L,
+                "%s: tr: continuous-kernel band %d outside [0, min(%d, L-1)] (dense kernels: unsupported)", fn,
+                tr->band, kMaxBand);
+  else
+    PMG_REQUIRE(tr->band >= 0 && tr->band <= kMaxBand,
+                "%s: tr: continuous-kernel band %d outside [0, %d] (dense kernels: unsupported)", fn, tr->band,
+                kMaxBand);
+  if (pick_J(tr->L) < 0) {
+    set_error("%s: L=%d > 1024 unsupported", fn, tr->L);
+    return PMG_EUNSUPPORTED;
+  }
+  return PMG_OK;
+}
 static inline int fill_params(FBParams& p, const pmg_transition* tr, int64_t T, int C, int B, double s,
                               double tol) {
   PMG_REQUIRE(tr && tr->L > 0 && tr->invz, "pmg fwd/bwd: bad transition");

@@ -30,6 +30,7 @@
 //   * total == 0 or not finite: the wave writes -1 into the rows it has not drawn yet and
 //     sets the sticky status word.  No LDS beyond the table, no grid barrier, no atomics.
 #include "fb_kernels.h"
+#include "segment_table.h"
 
 namespace pmg {
 
@@ -37,25 +38,18 @@ struct SampleParams {
   const float* alpha;      // (T, 2, L)
   const float* invz;       // (L)
   const float* uniforms;   // (R, T)
-  const int64_t* seg_off;  // (S + 1) row offsets
-  const int32_t* order;    // (S) segment of each group of R workgroups, or null
+  SegTable seg;            // the segments' rows (seg_off set), one per group of R workgroups
   int32_t* path_d;         // (R, T)
   int32_t* path_l;         // (R, T)
   int32_t* status;         // (1) sticky
   int64_t T;
-  int L, band, S, R;
+  int L, band, R;
   float A00, A01, A10, A11;
   float g[kMaxBand + 1];   // zero beyond the band
 };
 
 // ring depth: many waves per SIMD (one per sample), so a shallow ring; a slot is 2 J + 1 floats
 template <int J> constexpr int samp_pf() { return J >= 8 ? 2 : 4; }
-
-__device__ __forceinline__ int64_t samp_uniform_i64(int64_t v) {
-  const int lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)v);
-  const int hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
-}
 
 template <int J>
 struct SampRow {
@@ -98,13 +92,10 @@ __device__ __forceinline__ void seg_sample(const SampleParams& p, const float* s
   const int blk = blockIdx.x;
   const int grp = blk / p.R;
   const int r = blk - grp * p.R;
-  const int s = p.order ? __builtin_amdgcn_readfirstlane(p.order[grp]) : grp;
-  if ((unsigned)s >= (unsigned)p.S) return;
-  int64_t t_a = samp_uniform_i64(p.seg_off[s]);
-  int64_t t_b = samp_uniform_i64(p.seg_off[s + 1]);
-  t_a = t_a < 0 ? 0 : (t_a > p.T ? p.T : t_a);
-  t_b = t_b < t_a ? t_a : (t_b > p.T ? p.T : t_b);
-  if (t_a >= t_b) return;
+  int s;
+  int64_t t_a, t_b;
+  __builtin_assume(p.seg.seg_off != nullptr);   // the ragged set only: no equal-length branch here
+  if (!seg_rows(p.seg, p.T, grp, s, t_a, t_b) || t_a >= t_b) return;
   PMG_FB_LANE_SETUP
   const float* urow = p.uniforms + (int64_t)r * p.T;
   int32_t* pd = p.path_d + (int64_t)r * p.T;
@@ -258,35 +249,28 @@ int pmg_segment_sample(const float* alpha, int64_t T, const int64_t* seg_off, in
   PMG_REQUIRE((int64_t)S * R <= 0x7fffffffLL, "pmg_segment_sample: S=%d x R=%d workgroups exceed the grid", S, R);
   PMG_REQUIRE(alpha, "pmg_segment_sample: alpha is null");
   PMG_REQUIRE(seg_off, "pmg_segment_sample: seg_off is null");
-  PMG_REQUIRE(tr, "pmg_segment_sample: tr is null");
-  PMG_REQUIRE(tr->L > 0 && tr->invz, "pmg_segment_sample: tr: bad transition (L=%d, invz %s)", tr->L,
-              tr->invz ? "set" : "null");
-  PMG_REQUIRE(tr->band >= 0 && tr->band <= kMaxBand,
-              "pmg_segment_sample: tr: continuous-kernel band %d outside [0, %d] (dense kernels: unsupported)",
-              tr->band, kMaxBand);
+  const int tr_rc = check_banded_tr("pmg_segment_sample", tr, false);
+  if (tr_rc == PMG_EINVAL) return tr_rc;
   PMG_REQUIRE(uniforms, "pmg_segment_sample: uniforms is null");
   PMG_REQUIRE(path_d, "pmg_segment_sample: path_d is null");
   PMG_REQUIRE(path_l, "pmg_segment_sample: path_l is null");
   PMG_REQUIRE(status, "pmg_segment_sample: status is null");
+  if (tr_rc) return tr_rc;   // L > 1024
   const int J = pick_J(tr->L);
-  if (J < 0) {
-    set_error("pmg_segment_sample: L=%d > 1024 unsupported", tr->L);
-    return PMG_EUNSUPPORTED;
-  }
   SampleParams p;
   memset(&p, 0, sizeof(p));
   p.alpha = alpha;
   p.invz = tr->invz;
   p.uniforms = uniforms;
-  p.seg_off = seg_off;
-  p.order = order;
+  p.seg.seg_off = seg_off;
+  p.seg.order = order;
+  p.seg.S = S;
   p.path_d = path_d;
   p.path_l = path_l;
   p.status = status;
   p.T = T;
   p.L = tr->L;
   p.band = tr->band;
-  p.S = S;
   p.R = R;
   p.A00 = tr->A[0];
   p.A01 = tr->A[1];

@@ -21,15 +21,14 @@
 //   * workgroup b takes segment order[b] (longest first from the host): the long events
 //     then do not form the tail of the launch.  No LDS, no grid barrier, no atomic.
 #include "fb_kernels.h"
+#include "segment_table.h"
 
 namespace pmg {
 
 struct SegParams {
-  FBParams fb;             // emission, transition and outputs (alpha, logc, gamma, P)
-  const int64_t* seg_off;  // (S + 1) row offsets
-  const int32_t* order;    // (S) segment of each workgroup, or null
-  double* logz;            // (S)
-  int S;
+  FBParams fb;   // emission, transition and outputs (alpha, logc, gamma, P)
+  SegTable seg;  // the segments' rows (seg_off set)
+  double* logz;  // (S)
 };
 
 // ring depths: one wave per segment and ~2 waves per SIMD, so the ring alone hides the
@@ -38,26 +37,6 @@ struct SegParams {
 // whose 4-deep ring spilled to scratch at WP = 32
 template <int J> constexpr int seg_pf_fwd() { return J >= 16 ? 2 : (J >= 8 ? 4 : 8); }
 template <int J> constexpr int seg_pf_bwd() { return J >= 16 ? 2 : (J >= 8 ? 4 : 8); }
-
-__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
-  const int lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)v);
-  const int hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
-}
-
-// this workgroup's segment and its rows [a, b), clamped to 0 <= a <= b <= T (the entry
-// point cannot read the offsets); false: nothing to do
-__device__ __forceinline__ bool seg_rows(const SegParams& sp, int& s, int64_t& a, int64_t& b) {
-  const int blk = blockIdx.x;
-  s = sp.order ? __builtin_amdgcn_readfirstlane(sp.order[blk]) : blk;
-  if ((unsigned)s >= (unsigned)sp.S) return false;
-  a = uniform_i64(sp.seg_off[s]);
-  b = uniform_i64(sp.seg_off[s + 1]);
-  const int64_t T = sp.fb.T;
-  a = a < 0 ? 0 : (a > T ? T : a);
-  b = b < a ? a : (b > T ? T : b);
-  return true;
-}
 
 // ---------------------------------------------------------------------------
 // forward: steps t = a .. b-1 from the uniform state; alpha, logc, logz[s]
@@ -68,7 +47,8 @@ __device__ __forceinline__ void seg_forward(const SegParams& sp) {
   const FBParams& p = sp.fb;
   int s;
   int64_t t_a, t_b;
-  if (!seg_rows(sp, s, t_a, t_b)) return;
+  __builtin_assume(sp.seg.seg_off != nullptr);   // the ragged set only: no equal-length branch here
+  if (!seg_rows(sp.seg, p.T, blockIdx.x, s, t_a, t_b)) return;
   if (t_a >= t_b) {
     if (threadIdx.x == 0) sp.logz[s] = 0.0;
     return;
@@ -159,7 +139,8 @@ __device__ __forceinline__ void seg_backward(const SegParams& sp) {
   const FBParams& p = sp.fb;
   int s;
   int64_t t_a, t_b;
-  if (!seg_rows(sp, s, t_a, t_b)) return;
+  __builtin_assume(sp.seg.seg_off != nullptr);   // the ragged set only: no equal-length branch here
+  if (!seg_rows(sp.seg, p.T, blockIdx.x, s, t_a, t_b)) return;
   if (t_a >= t_b) return;
   PMG_FB_LANE_SETUP
   (void)lane;
@@ -224,19 +205,6 @@ __global__ void __launch_bounds__(64) k_segment_backward(SegParams sp) {
 // ---------------------------------------------------------------------------
 // host dispatch
 // ---------------------------------------------------------------------------
-// the Viterbi band table: band = ceil(8.31 mv) is 5 (mv 0.5), 9 (mv 1, the default),
-// 17 (mv 2); wider ones share 32
-static int seg_WP(int band) {
-  if (band <= 5) return 5;
-  if (band <= 9) return 9;
-  if (band <= 17) return 17;
-  return 32;
-}
-
-#define PMG_SEG_ALL(X)                                                                      \
-  X(1, 5) X(1, 9) X(1, 17) X(1, 32) X(2, 5) X(2, 9) X(2, 17) X(2, 32) X(4, 5) X(4, 9)       \
-  X(4, 17) X(4, 32) X(8, 5) X(8, 9) X(8, 17) X(8, 32) X(16, 5) X(16, 9) X(16, 17) X(16, 32)
-
 typedef void (*seg_kernel_t)(SegParams);
 static void seg_kernels(int J, int WP, seg_kernel_t* fwd, seg_kernel_t* bwd) {
   *fwd = nullptr;
@@ -246,7 +214,7 @@ static void seg_kernels(int J, int WP, seg_kernel_t* fwd, seg_kernel_t* bwd) {
     *fwd = k_segment_forward<JJ, WW>;     \
     *bwd = k_segment_backward<JJ, WW>;    \
   }
-  PMG_SEG_ALL(PMG_SEG_CASE)
+  PMG_WAVE_ALL(PMG_SEG_CASE)
 #undef PMG_SEG_CASE
 }
 
@@ -267,20 +235,13 @@ int pmg_segment_smoother(const float* delta, const float* phi, const double* m, 
   PMG_REQUIRE(phi, "pmg_segment_smoother: phi is null");
   PMG_REQUIRE(m, "pmg_segment_smoother: m is null");
   PMG_REQUIRE(seg_off, "pmg_segment_smoother: seg_off is null");
-  PMG_REQUIRE(tr, "pmg_segment_smoother: tr is null");
-  PMG_REQUIRE(tr->L > 0 && tr->invz, "pmg_segment_smoother: tr: bad transition (L=%d, invz %s)", tr->L,
-              tr->invz ? "set" : "null");
-  PMG_REQUIRE(tr->band >= 0 && tr->band <= kMaxBand,
-              "pmg_segment_smoother: tr: continuous-kernel band %d outside [0, %d] (dense kernels: unsupported)",
-              tr->band, kMaxBand);
+  const int tr_rc = check_banded_tr("pmg_segment_smoother", tr, false);
+  if (tr_rc == PMG_EINVAL) return tr_rc;
   PMG_REQUIRE(likelihood_scale == likelihood_scale, "pmg_segment_smoother: likelihood_scale is NaN");
   PMG_REQUIRE(alpha, "pmg_segment_smoother: alpha is null");
   PMG_REQUIRE(logc, "pmg_segment_smoother: logc is null");
   PMG_REQUIRE(logz, "pmg_segment_smoother: logz is null");
-  if (pick_J(tr->L) < 0) {
-    set_error("pmg_segment_smoother: L=%d > 1024 unsupported", tr->L);
-    return PMG_EUNSUPPORTED;
-  }
+  if (tr_rc) return tr_rc;   // L > 1024
   SegParams sp;
   memset(&sp, 0, sizeof(sp));
   const int rc = fill_params(sp.fb, tr, T, 1, 0, likelihood_scale, 0.0);
@@ -294,12 +255,12 @@ int pmg_segment_smoother(const float* delta, const float* phi, const double* m, 
   p.logc = logc;
   p.gamma = gamma;
   p.P = P;
-  sp.seg_off = seg_off;
-  sp.order = order;
+  sp.seg.seg_off = seg_off;
+  sp.seg.order = order;
+  sp.seg.S = S;
   sp.logz = logz;
-  sp.S = S;
   seg_kernel_t kf, kb;
-  seg_kernels(p.Lpad / 64, seg_WP(tr->band), &kf, &kb);
+  seg_kernels(p.Lpad / 64, wave_WP(tr->band), &kf, &kb);
   PMG_REQUIRE(kf && kb, "pmg_segment_smoother: no kernel for J=%d band=%d", p.Lpad / 64, tr->band);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(kf, dim3(S), dim3(64), 0, st, sp);

@@ -1,8 +1,7 @@
-// Device code and host tables shared by the max-plus (Viterbi) kernel sets: the
-// single-sequence / equal-length batch of viterbi.hip and the ragged segments of
-// segment_viterbi.hip.  Every function here works on ONE chain (VitSeq / VitSeg: its
-// first row, its row count and its index), so that both kernel sets run the same
-// arithmetic in the same order: a chain's outputs do not depend on which set walked it.
+// Device code of the max-plus (Viterbi) kernels of viterbi.hip.  Every function here works
+// on ONE chain (VitChain: its index, its first row and its row count), whether it is one of
+// equal-length stacked sequences or a ragged segment: a chain's outputs depend on its own
+// rows alone.
 //
 // The recurrence is filter_one_step (decoder.py:151-172) with each logsumexp replaced
 // by a max (the reference has no Viterbi of its own), over the device transition of
@@ -13,18 +12,23 @@
 //   delta_'[d'][j] = v_d'[j] + s*delta[t,j] + phi[t,j/32]
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #include "fb_kernels.h"
 
 namespace pmg {
 
 struct VitParams {
-  const float* delta;     // (R T, L)
-  const float* phi;       // (R T, nblk)
-  const double* rblk;     // (R T, nblk)
+  const float* delta;     // (T, L)
+  const float* phi;       // (T, nblk)
+  const double* rblk;     // (T, nblk)
   const float* invz;      // (L)
   const double* log_pi0;  // (2, L)
-  int64_t T;
+  int64_t T;              // rows of the call, all chains together
+  // R: chains in the call.  No kernel reads it: it is padding.  With the tables below 4 bytes
+  // earlier, the compiler's register allocation for (J, WP) = (4, 5) and (4, 9) comes out 1-2
+  // VGPRs higher and loses a wave of occupancy (seen in the compiler's resource remarks; the
+  // reason is not understood).  The static_assert below pins the offset.
   int L, Lpad, nblk, band, R;
   float lg[kMaxBand + 1];  // log g[k] (-inf beyond the band)
   float la[4];             // log A00 A01 A10 A11 (-inf allowed)
@@ -32,14 +36,15 @@ struct VitParams {
   double lg64[kMaxBand + 1];
   double la64[4];
   double logL64, s64;
-  uint8_t* bp;    // [R][T][Lpad] back-pointer bytes (row 0 of a sequence is not used)
-  int32_t* jp;    // [R][T] jump back-pointers
-  int32_t* last;  // [R][2] the final (d, l)
-  double* inc;    // [R][T] per-step increments of the path score
+  uint8_t* bp;    // [T][Lpad] back-pointer bytes (row 0 of a chain is not used)
+  int32_t* jp;    // [T] jump back-pointers
+  int32_t* last;  // [chains][2] the final (d, l)
+  double* inc;    // [T] per-step increments of the path score
   int32_t* path_d;
   int32_t* path_l;
   double* log_joint;
 };
+static_assert(offsetof(VitParams, lg) == 68, "VitParams: see the comment on R before moving lg");
 
 template <int J> constexpr int vit_pf() { return J >= 16 ? 2 : 4; }
 
@@ -49,18 +54,11 @@ struct VitRow {
   float ph;
 };
 
-// A chain: the rows one wave walks.  base(p): its first row among the call's rows; n(p):
-// its row count (>= 1); id: its index in `last` (and log_joint).
-struct VitSeq {   // sequence r of R equal-length ones stacked in time
-  int id;
-  __device__ __forceinline__ int64_t base(const VitParams& p) const { return (int64_t)id * p.T; }
-  __device__ __forceinline__ int64_t n(const VitParams& p) const { return p.T; }
-};
-struct VitSeg {   // rows [a, a + len) of a ragged set
+// A chain: the rows [a, a + len) one wave walks (len >= 1); id: its index in `last` (and
+// log_joint).  All three are wave-uniform.
+struct VitChain {
   int id;
   int64_t a, len;
-  __device__ __forceinline__ int64_t base(const VitParams&) const { return a; }
-  __device__ __forceinline__ int64_t n(const VitParams&) const { return len; }
 };
 
 // row t of the chain whose first emission rows are `delta` / `phi`
@@ -166,15 +164,15 @@ __device__ __forceinline__ void store_codes(uint8_t* row, int Lpad, int j0, cons
 // The forward scan of one chain by one wave; last[2 id ..] receives the final (d, l).
 // Every ring address is clamped to the chain's own last row, and rows 1 .. n-1 of its bp /
 // jp are written (row 0 has no back-pointers): no access leaves the chain's rows.
-template <int J, int WP, int VEC, class Chain>
-__device__ __forceinline__ void vit_forward(const VitParams& p, const Chain& ch) {
+template <int J, int WP, int VEC>
+__device__ __forceinline__ void vit_forward(const VitParams& p, const VitChain& ch) {
   constexpr int PF = vit_pf<J>();
   const float ninf = -INFINITY;
   const int j0 = (int)threadIdx.x * J;
-  const float* delta = p.delta + ch.base(p) * p.L;
-  const float* phi = p.phi + ch.base(p) * p.nblk;
-  uint8_t* bp = p.bp + ch.base(p) * p.Lpad;
-  int32_t* jp = p.jp + ch.base(p);
+  const float* delta = p.delta + ch.a * p.L;
+  const float* phi = p.phi + ch.a * p.nblk;
+  uint8_t* bp = p.bp + ch.a * p.Lpad;
+  int32_t* jp = p.jp + ch.a;
   const int shift = WP - p.band;   // code of band_max -> i - j + band
 
   bool ok[J];
@@ -205,8 +203,8 @@ __device__ __forceinline__ void vit_forward(const VitParams& p, const Chain& ch)
       d1[j] = ok[j] ? (float)(lp1[j] - c0) + em : ninf;
     }
   }
-  if (ch.n(p) > 1) {
-    const int64_t last = ch.n(p) - 1;
+  if (ch.len > 1) {
+    const int64_t last = ch.len - 1;
     VitRow<J> ring[PF];
 #pragma unroll
     for (int q = 0; q < PF; ++q) vit_load<J, VEC>(p, delta, phi, 1 + q < last ? 1 + q : last, j0, ring[q]);
@@ -260,13 +258,13 @@ __device__ __forceinline__ void vit_forward(const VitParams& p, const Chain& ch)
       __builtin_amdgcn_raw_buffer_store_b32((uint32_t)jw, rs, threadIdx.x == 0 ? 0 : 64, 0, 0);
     };
     int64_t tb = 1;
-    for (; tb + PF <= ch.n(p); tb += PF) {
+    for (; tb + PF <= ch.len; tb += PF) {
 #pragma unroll
       for (int q = 0; q < PF; ++q) body(q, tb + q, true);
     }
 #pragma unroll
     for (int q = 0; q < PF; ++q)
-      if (tb + q < ch.n(p)) body(q, tb + q, false);
+      if (tb + q < ch.len) body(q, tb + q, false);
   }
   // the final state: argmax over the flattened (2, L) scores (first index on ties)
   float l0 = ninf, l1 = ninf;
@@ -296,16 +294,15 @@ __device__ __forceinline__ void vit_forward(const VitParams& p, const Chain& ch)
 // 64); the 16-byte loads are clamped to the chain's own last 16-byte group and the jp loads
 // to its last row.  Uses 16.25 KiB of the workgroup's LDS.
 constexpr int kTracePieceBytes = 16384;
-template <class Chain>
-__device__ __forceinline__ void vit_trace(const VitParams& p, const Chain& ch) {
+__device__ __forceinline__ void vit_trace(const VitParams& p, const VitChain& ch) {
   __shared__ __attribute__((aligned(16))) uint8_t rows[kTracePieceBytes];
   __shared__ int32_t jrow[64];
   const int lane = threadIdx.x;
   const int Lpad = p.Lpad;
   const int NP = kTracePieceBytes / Lpad < 64 ? kTracePieceBytes / Lpad : 64;
   const int nv = NP * Lpad / 1024;
-  const int64_t n = ch.n(p);
-  const int64_t row0 = ch.base(p);
+  const int64_t n = ch.len;
+  const int64_t row0 = ch.a;
   const uint8_t* bp = p.bp + row0 * Lpad;
   const int32_t* jp = p.jp + row0;
   const int64_t end = n * Lpad - 16;   // the last 16-byte group of this chain's rows
@@ -408,29 +405,8 @@ __device__ __forceinline__ double vit_sum(const double* inc, int64_t n, double* 
 }
 
 // ---------------------------------------------------------------------------
-// host tables
+// host
 // ---------------------------------------------------------------------------
-static int vit_J(int L) {
-  if (L <= 0) return -1;
-  if (L <= 64) return 1;
-  if (L <= 128) return 2;
-  if (L <= 256) return 4;
-  if (L <= 512) return 8;
-  if (L <= 1024) return 16;
-  return -1;
-}
-// band = ceil(8.31 mv): 5 (mv 0.5), 9 (mv 1, the default), 17 (mv 2); wider ones share 32
-static int vit_WP(int band) {
-  if (band <= 5) return 5;
-  if (band <= 9) return 9;
-  if (band <= 17) return 17;
-  return 32;
-}
-
-#define PMG_VIT_ALL(X)                                                                      \
-  X(1, 5) X(1, 9) X(1, 17) X(1, 32) X(2, 5) X(2, 9) X(2, 17) X(2, 32) X(4, 5) X(4, 9)       \
-  X(4, 17) X(4, 32) X(8, 5) X(8, 9) X(8, 17) X(8, 32) X(16, 5) X(16, 9) X(16, 17) X(16, 32)
-
 // the transition's logs (f32 for the scan, f64 for the score), the shape and the scale;
 // the caller sets the emission, workspace and output pointers, T and R
 static void vit_fill_params(VitParams& p, const pmg_transition* tr, int J, double likelihood_scale) {

@@ -866,26 +866,45 @@ class DeviceEM:
         with self._t('backward_repair'):         # verify / relaxation
             nat.check(self.lib.pmg_backward_smoother_phase(*args, 2 | ad | self._seg_bits()), "pmg_backward_smoother")
 
+    def _need_banded(self, what):
+        if self.dense or self._tr_c is None:
+            raise NotImplementedError(f"{what} needs a banded transition (set_transition with a BandedTransition)")
+
+    @staticmethod
+    def _n_segments(seg_off, order):
+        """S of a (S + 1,) int64 seg_off and an (S,) int32 order (or None), both device tensors."""
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
+            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
+        S = seg_off.numel() - 1
+        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
+            raise ValueError(f"order must be a ({S},) int32 device tensor")
+        return S
+
+    def _viterbi_buffers(self, size_fn, T, chains, chains_name, path_shape):
+        """Workspace (size_fn(T, L, chains) bytes), log_pi0 and the outputs path_d, path_l
+        (path_shape) int32 and log_joint (chains,) float64 of a Viterbi call."""
+        need = int(size_fn(T, self.L, chains))
+        if need == 0:
+            raise nat.NativeError(f"{size_fn.__name__}(T={T}, L={self.L}, {chains_name}={chains}) returned 0")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        log_pi0 = torch.as_tensor(viterbi_log_pi0(self._tr), device=self.dev)
+        path_d = torch.empty(path_shape, dtype=torch.int32, device=self.dev)
+        path_l = torch.empty(path_shape, dtype=torch.int32, device=self.dev)
+        lj = torch.empty(chains, dtype=torch.float64, device=self.dev)
+        return ws, log_pi0, path_d, path_l, lj
+
     def viterbi(self, likelihood_scale, n_seq=1):
         """Most likely (dynamics, latent) path under the banded transition
         (pmg_viterbi_decode), after emission() with the same likelihood_scale.  n_seq > 1:
         the spikes are n_seq equal-length sequences stacked in time, decoded in one launch.
         Returns device tensors path_d, path_l (n_seq, T / n_seq) int32 and log_joint
         (n_seq,) float64."""
-        if self.dense or self._tr_c is None:
-            raise NotImplementedError("viterbi needs a banded transition (set_transition with a BandedTransition)")
+        self._need_banded("viterbi")
         R = int(n_seq)
         if R < 1 or self.T % R:
             raise ValueError("stacked sequences must have equal length")
         T = self.T // R
-        need = int(self.lib.pmg_viterbi_workspace_size(T, self.L, R))
-        if need == 0:
-            raise nat.NativeError(f"pmg_viterbi_workspace_size(T={T}, L={self.L}, R={R}) returned 0")
-        ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        log_pi0 = torch.as_tensor(viterbi_log_pi0(self._tr), device=self.dev)
-        path_d = torch.empty((R, T), dtype=torch.int32, device=self.dev)
-        path_l = torch.empty((R, T), dtype=torch.int32, device=self.dev)
-        lj = torch.empty(R, dtype=torch.float64, device=self.dev)
+        ws, log_pi0, path_d, path_l, lj = self._viterbi_buffers(self.lib.pmg_viterbi_workspace_size, T, R, 'R', (R, T))
         with self._t('viterbi'):
             nat.check(self.lib.pmg_viterbi_decode(nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.rblk), T, R,
                                                   ctypes.byref(self._tr_c), nat.ptr(log_pi0), float(likelihood_scale),
@@ -903,18 +922,12 @@ class DeviceEM:
         the engine (offsets and outputs relative to r0).  Returns device tensors
         (alpha (T, 2, L) -- the engine's buffer --, logc (T,), logz (S,) float64); rows that no
         segment owns are left as they were."""
-        if self.dense or self._tr_c is None:
-            raise NotImplementedError("segment_smoother needs a banded transition (set_transition with a "
-                                      "BandedTransition)")
+        self._need_banded("segment_smoother")
         r0, r1 = (0, self.T) if rows is None else (int(rows[0]), int(rows[1]))
         if not 0 <= r0 < r1 <= self.T:
             raise ValueError(f"rows {(r0, r1)} outside [0, {self.T}]")
         T = r1 - r0
-        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
-            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
-        S = seg_off.numel() - 1
-        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
-            raise ValueError(f"order must be a ({S},) int32 device tensor")
+        S = self._n_segments(seg_off, order)
         for name, t, shape in (('gamma', gamma, (T, 2, self.L)), ('P', P, (T, self.L))):
             if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
                 raise ValueError(f"{name} must be a {shape} float32 device tensor")
@@ -936,23 +949,11 @@ class DeviceEM:
         tensors path_d, path_l (T,) int32 -- rows that no segment owns are left unset -- and
         log_joint (S,) float64; each segment's outputs equal viterbi() on its rows alone bit
         for bit."""
-        if self.dense or self._tr_c is None:
-            raise NotImplementedError("segment_viterbi needs a banded transition (set_transition with a "
-                                      "BandedTransition)")
+        self._need_banded("segment_viterbi")
         T = self.T
-        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
-            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
-        S = seg_off.numel() - 1
-        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
-            raise ValueError(f"order must be a ({S},) int32 device tensor")
-        need = int(self.lib.pmg_segment_viterbi_workspace_size(T, self.L, S))
-        if need == 0:
-            raise nat.NativeError(f"pmg_segment_viterbi_workspace_size(T={T}, L={self.L}, S={S}) returned 0")
-        ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        log_pi0 = torch.as_tensor(viterbi_log_pi0(self._tr), device=self.dev)
-        path_d = torch.empty(T, dtype=torch.int32, device=self.dev)
-        path_l = torch.empty(T, dtype=torch.int32, device=self.dev)
-        lj = torch.empty(S, dtype=torch.float64, device=self.dev)
+        S = self._n_segments(seg_off, order)
+        ws, log_pi0, path_d, path_l, lj = self._viterbi_buffers(self.lib.pmg_segment_viterbi_workspace_size, T, S,
+                                                                'S', T)
         with self._t('segment_viterbi'):
             nat.check(self.lib.pmg_segment_viterbi(nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.rblk), T,
                                                    nat.ptr(seg_off), S, nat.ptr(order), ctypes.byref(self._tr_c),
@@ -971,15 +972,9 @@ class DeviceEM:
         path_l (R, T) int32, -1 in rows that no segment owns.  Raises NativeError when a
         step's weights summed to 0 or to a non-finite value (the device status word; the read
         syncs)."""
-        if self.dense or self._tr_c is None:
-            raise NotImplementedError("segment_sampler needs a banded transition (set_transition with a "
-                                      "BandedTransition)")
+        self._need_banded("segment_sampler")
         T = self.T
-        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 2:
-            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
-        S = seg_off.numel() - 1
-        if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (S,)):
-            raise ValueError(f"order must be a ({S},) int32 device tensor")
+        S = self._n_segments(seg_off, order)
         if (not isinstance(uniforms, torch.Tensor) or uniforms.dtype != torch.float32 or uniforms.dim() != 2
                 or uniforms.shape[0] < 1 or uniforms.shape[1] != T):
             raise ValueError(f"uniforms must be a (n_samples >= 1, {T}) float32 device tensor")

@@ -1,4 +1,4 @@
-"""decode_latent_segments_viterbi / pmg_segment_viterbi (csrc/segment_viterbi.hip) on the
+"""decode_latent_segments_viterbi / pmg_segment_viterbi (csrc/viterbi.hip) on the
 device: the MAP paths of many ragged events in one call.
 
 Every case is one (N, L) shape -- the smallest that reach each lane layout J in {1, 2, 4, 8,

@@ -152,6 +152,25 @@ def test_batched_sequences_equal_single_calls_bit_for_bit():
     assert len({float(x) for x in rb['log_joint_map']}) == 3
 
 
+def test_short_stacked_sequences_at_unaligned_L():
+    """R = 3 sequences of T = 5 rows at L = 65 (J = 2, two of 128 padded latents used, the
+    scalar row loads; T is no multiple of the ring depth): chain r of the equal-length table
+    starts at row r T, and each equals its own single call bit for bit."""
+    N, L, T = 12, 65, 5
+    ds = [_data(N, L, T, seed=s) for s in (1, 11, 21)]
+    tun = ds[0]['tuning']
+    m = PoissonGPLVMJump1D(N, n_latent_bin=L)
+    rb = m.decode_latent_viterbi(np.stack([d['y'] for d in ds]), tuning=tun)
+    assert rb['map_latent'].shape == (3, T) and rb['log_joint_map'].shape == (3,)
+    for r in range(3):
+        one = m.decode_latent_viterbi(ds[r]['y'], tuning=tun)
+        assert np.array_equal(one['map_dynamics'], rb['map_dynamics'][r])
+        assert np.array_equal(one['map_latent'], rb['map_latent'][r])
+        assert one['log_joint_map'] == rb['log_joint_map'][r]
+        assert np.isfinite(one['log_joint_map'])
+    assert len({float(x) for x in rb['log_joint_map']}) == 3
+
+
 def test_deterministic():
     res1 = _run_case(CASES['j2_jumpy'])[0]
     res2 = _run_case(CASES['j2_jumpy'])[0]

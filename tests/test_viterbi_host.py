@@ -115,6 +115,28 @@ def test_c_abi_workspace_and_argument_checks():
     assert rc == -1 and b'invz' in msg
 
 
+def test_workspace_sizes_of_the_two_entries_agree():
+    """One carver serves both entries: R stacked sequences of T rows need what R segments over
+    R T rows need, namely the back-pointer bytes, jump words, final states and f64 increments,
+    each slice starting 256-byte aligned, plus 256; 0 on every degenerate argument."""
+    lib = _native.load()
+    seq, seg = lib.pmg_viterbi_workspace_size, lib.pmg_segment_viterbi_workspace_size
+
+    def want(rows, L, chains):
+        lpad = 64 * next(j for j in (1, 2, 4, 8, 16) if L <= 64 * j)
+        off = 0
+        for nbytes in (rows * lpad, 4 * rows, 8 * chains, 8 * rows):
+            off = (off + 255) // 256 * 256 + nbytes
+        return off + 256
+
+    for T, L, R in [(1, 1, 1), (5, 65, 3), (200, 64, 7), (1000, 512, 1), (37, 1024, 65535), (3, 100, 2)]:
+        assert seq(T, L, R) == seg(R * T, L, R) == want(R * T, L, R), (T, L, R)
+    assert seg(200, 64, 70000) == want(200, 64, 70000)          # only the stacked entry bounds R
+    for T, L, R in [(0, 64, 1), (-1, 64, 1), (10, 0, 1), (10, -5, 1), (10, 1025, 1), (10, 64, 0), (10, 64, -2)]:
+        assert seq(T, L, R) == 0 and seg(T, L, R) == 0, (T, L, R)
+    assert seq(10, 64, 65536) == 0
+
+
 def test_dense_transition_is_refused_on_the_host():
     """A custom kernel, a band wider than 32 bins or n_latent_bin > 1024 resolve to the
     dense scans, which have no MAP decoder: NotImplementedError before any device object
