@@ -1080,13 +1080,6 @@ static DenseWork carve_dense(void* ws, int64_t T, int Lp, int C, size_t* total =
   return w;
 }
 
-static int dense_cus() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 64;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 64;
-  return n;
-}
-
 static int dense_params(DenseParams& p, const pmg_dense_transition* tr, int64_t T, int C, int B, double s,
                         double tol) {
   PMG_REQUIRE(tr && tr->L > 0 && tr->logK && tr->logKT && tr->logK_lo && tr->logKT_lo,
@@ -1114,7 +1107,7 @@ static int dense_params(DenseParams& p, const pmg_dense_transition* tr, int64_t 
   p.B = B;
   p.M = (int)((T + C - 1) / C);
   p.tol = (float)tol;
-  int S = dense_cus();
+  int S = device_cu_count();
   if (S > kDMaxSeg) S = kDMaxSeg;
   if (S > p.M) S = p.M;
   p.G = (p.M + S - 1) / S;

@@ -85,20 +85,8 @@ static FBWork carve_fb(void* ws, int64_t T, int Lpad, int C, size_t* total = nul
 
 // Relaxation segments: at most one single-wave workgroup per CU (so all are resident
 // whatever else the device runs: 64 threads, no LDS), G chunks each.
-static int device_cus() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 64;
-  if (!cached[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 64;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
 static void relax_shape(FBParams& p) {
-  int S = device_cus();
+  int S = device_cu_count();
   if (S > kRelaxMaxSeg) S = kRelaxMaxSeg;
   if (S > p.M) S = p.M;
   if (S < 1) S = 1;
@@ -148,7 +136,7 @@ static int batch_params(FBParams& p, int R, int64_t T, int chunk, size_t workspa
   p.ldphi = R * p.nblk;
   p.ldm = R;
   p.ws_stride = (int64_t)*slab;
-  int S = device_cus() / R;
+  int S = device_cu_count() / R;
   if (S < 1) S = 1;
   if (S > p.S) S = p.S;
   p.G = (p.M + S - 1) / S;
@@ -161,7 +149,7 @@ static void requested_segments(FBParams& p, int phase, int R) {
   int S = (phase >> 16) & 0xfff;
   if (S <= 0) return;
   if (S > kRelaxMaxSeg) S = kRelaxMaxSeg;
-  const int cap = 2 * device_cus() / (R > 1 ? R : 1);   // all R S single-wave groups co-resident
+  const int cap = 2 * device_cu_count() / (R > 1 ? R : 1);   // all R S single-wave groups co-resident
   if (S > cap) S = cap > 0 ? cap : 1;
   if (S > p.M) S = p.M;
   p.G = (p.M + S - 1) / S;

@@ -783,12 +783,10 @@ struct AdamWork {
   int* xflag;
 };
 
-static int num_cus();
-
 // G <= #CUs workgroups (all co-resident): the partial arrays and the row-block exchange
 // are sized for #CUs, so one size serves every row-block split of a shape
 static size_t adam_ws(int G, int maxiter, AdamWork* w, void* base) {
-  const int cus = num_cus();
+  const int cus = device_cu_count();
   const size_t Gw = (size_t)(G > cus ? G : cus);
   Carver c(base);
   AdamWork ww;
@@ -843,17 +841,10 @@ static AdamKernel pick_adam(int NB, int L, int S) {
 
 static int adam_row_blocks(int L) { return L <= 512 ? 1 : (L + 255) / 256; }
 
-static int num_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-  return cus > 0 ? cus : 256;
-}
-
 // RB row blocks x Gg neuron groups of S neurons, G = RB Gg <= #CUs
 static void adam_geometry(int N, int L, int NB, int& S, int& G, int& ng, int& LG, int* RBo = nullptr,
                           int* Ggo = nullptr) {
-  const int cus = num_cus();
+  const int cus = device_cu_count();
   const int RB = adam_row_blocks(L);
   const int gmax = cus / RB > 0 ? cus / RB : 1;
   S = (N + gmax - 1) / gmax;
@@ -873,7 +864,7 @@ static void adam_geometry(int N, int L, int NB, int& S, int& G, int& ng, int& LG
 // (up to kSMax, while the kernel still fits) so that more restarts share a launch.
 static void adam_batch_geometry(int N, int L, int NB, int R, int& S, int& G, int& ng, int& LG, int& Rg) {
   adam_geometry(N, L, NB, S, G, ng, LG);
-  const int cus = num_cus();
+  const int cus = device_cu_count();
   if (R > 1) {
     int want = (int)(((int64_t)R * N + cus - 1) / cus);
     if (want == 3) want = 4;
@@ -907,7 +898,7 @@ int pmg_mstep_adam_supported(int32_t L, int32_t NB, int32_t N) {
   if (L <= 0 || L > 2 * kThreads || NB <= 0 || N <= 0) return 0;
   int S, G, ng, LG;
   adam_geometry(N, L, NB, S, G, ng, LG);
-  if (S > kSMax || NB * S > kThreads || G > num_cus()) return 0;
+  if (S > kSMax || NB * S > kThreads || G > device_cu_count()) return 0;
   AdamKernel kern = pick_adam(NB, L, S);
   return (kern.fn != nullptr && kern.lds <= 160 * 1024) ? 1 : 0;
 }
@@ -926,7 +917,8 @@ static int adam_run(double* W, double* mu, double* nu, int64_t* count, const flo
   adam_batch_geometry(N, L, NB, R, S, G, ng, LG, Rg);
   int RB = 1, Gg = G;
   if (R == 1) adam_geometry(N, L, NB, S, G, ng, LG, &RB, &Gg);
-  PMG_REQUIRE(G <= num_cus(), "pmg_mstep_adam: %d workgroups (%d row blocks) exceed the %d CUs", G, RB, num_cus());
+  PMG_REQUIRE(G <= device_cu_count(), "pmg_mstep_adam: %d workgroups (%d row blocks) exceed the %d CUs", G, RB,
+              device_cu_count());
   PMG_REQUIRE(S <= kSMax, "pmg_mstep_adam: N=%d needs %d neurons per workgroup (> %d)", N, S, kSMax);
   PMG_REQUIRE(NB * S <= kThreads, "pmg_mstep_adam: NB*S=%d > %d", NB * S, kThreads);
   AdamKernel kern = pick_adam(NB, L, S);

@@ -58,15 +58,19 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 // EM iteration over the five persistent launches, 890 -> 827 EM it/s, so it is opt-in;
 // without it, a grid kept off part of the device by other work ends its bounded spins
 // with PMG_ETIMEOUT rather than hanging).
+//
+// The current device's CU count, cached per device.  It sizes the grids that must be
+// co-resident, so a failed query falls back to 64: under-counting is the safe direction.
 static inline int device_cu_count() {
-  static int ncu = 0;
-  if (ncu <= 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
+  static int cached[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 64;
+  if (!cached[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 64;
+    cached[dev] = n;
   }
-  return ncu;
+  return cached[dev];
 }
 
 static inline bool coop_launch_enabled() {

@@ -678,17 +678,6 @@ __global__ void __launch_bounds__(256) k_spikes_bf16t(const float* __restrict__ 
   }
 }
 
-static int device_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
-  return ncu;
-}
-
 // One workgroup per CU (the kernel runs at one wave per SIMD: 73.7 KB LDS, 406
 // registers), all in ONE round: tiles x K-slices <= #CUs.
 static int ptb3_geometry(int64_t K, int Mdim, int Ndim, int& nMT, int& nNT, int& nKS, int64_t& KT,
@@ -698,7 +687,7 @@ static int ptb3_geometry(int64_t K, int Mdim, int Ndim, int& nMT, int& nNT, int&
   Mp = nMT * TM;
   Npd = nNT * TN;
   const int64_t tiles = (int64_t)nMT * nNT;
-  int64_t want = device_cus() / tiles;
+  int64_t want = device_cu_count() / tiles;
   if (want < 1) want = 1;
   KT = (K + want - 1) / want;
   KT = round_up(KT < kFlush ? kFlush : KT, kFlush);

@@ -245,90 +245,74 @@ class _NoTimer:
 _NO_TIMER = _NoTimer()
 
 
-class DeviceEM:
-    """One fit's device state: spikes, basis, transition, workspaces, buffers."""
+def ctl_view(ws, R, r):
+    """Sequence r's int32 control words in a scan workspace of R slabs (device view; see
+    fb_kernels.h kCtl*).  batch_params in fwdbwd.hip defines the slab."""
+    slab = (ws.numel() // R) & ~255 if R > 1 else ws.numel()
+    return ws[r * slab:r * slab + 4 * nat.CTL_WORDS].view(torch.int32)
 
-    def __init__(self, spikes: SpikeData, L: int, basis=None, scan: ScanConfig | None = None):
-        self.lib = nat.load()
-        self.sp = spikes
-        self.dev = spikes.device
-        self.T, self.N, self.L = spikes.T, spikes.N, int(L)
-        self.scan = scan or ScanConfig()
-        self.C = self.scan.chunk_for(self.T)
-        self.Cb = self.scan.chunk_bwd_for(self.T)
-        self.nblk = _ru(self.L, 32) // 32
-        T, L, N, dev = self.T, self.L, self.N, self.dev
-        f32, f64 = torch.float32, torch.float64
-        self.basis = None
-        if basis is not None:
-            b = np.ascontiguousarray(basis, dtype=np.float32)
-            if b.shape[0] != L:
-                raise ValueError("basis must have n_latent_bin rows")
-            self.NB = int(b.shape[1])
-            self.basis = torch.as_tensor(b, device=dev)
-        self.delta = torch.empty((T, L), dtype=f32, device=dev)
-        self.rblk = torch.empty((T, self.nblk), dtype=f64, device=dev)
-        self.phi = torch.empty((T, self.nblk), dtype=f32, device=dev)
-        self.mref = torch.empty(T, dtype=f64, device=dev)
-        self.alpha = torch.empty((T, 2, L), dtype=f32, device=dev)
-        self.logc = torch.empty(T, dtype=f64, device=dev)
-        self._P = torch.empty((T, L), dtype=f32, device=dev)
-        # integer spikes: the backward writes P as its three exact bf16 planes, the operands
-        # of the statistics GEMMs (PMG_PHASE_P_BF16X3), instead of f32 P
-        self.use_planes = bool(self.PLANES and spikes.ybt is not None and planes_ok(T, L))
-        self.Pq = torch.empty((3, T, L), dtype=torch.int16, device=dev) if self.use_planes else None
-        self._p_fresh = 'f32'       # which of _P / Pq holds the current posterior marginal
-        self.tuning64 = torch.empty((L, N), dtype=f64, device=dev)
-        self.tuning32 = torch.empty((L, N), dtype=f32, device=dev)
-        self.yw = torch.empty((L, N), dtype=f64, device=dev)
-        self.tw = torch.empty(L, dtype=f64, device=dev)
-        # zero-filled once: it holds the emission's sticky range flag (include/pmg.h)
-        self.ws_em = torch.zeros(int(self.lib.pmg_emission_workspace_size(T, L, N)), dtype=torch.uint8, device=dev)
-        self._em_flag = _flag_view(self.lib, self.ws_em, T, L, N)
-        # zero-filled once (include/pmg.h): the scan kernels keep its control words zero
-        self.ws_fb = torch.zeros(int(self.lib.pmg_fwdbwd_workspace_size(T, L, min(self.C, self.Cb))),
-                                 dtype=torch.uint8, device=dev)
-        ss_bytes = (max(self.lib.pmg_suffstats_bf16_workspace_size(T, L, N),
-                        self.lib.pmg_suffstats_bf16x3_workspace_size(T, L, N) if self.use_planes else 0)
-                    if spikes.ybt is not None
-                    else self.lib.pmg_suffstats_workspace_size(T, L, spikes.Np))
-        self.ws_ss = torch.empty(int(ss_bytes), dtype=torch.uint8, device=dev)
-        if self.ws_fb.numel() == 0 and L <= 1024:
-            raise nat.NativeError(f"pmg_fwdbwd_workspace_size(T={T}, L={L}) returned 0")
-        # L > 1024: only the dense log-domain scans (set_transition refuses a banded one)
-        self.ws_ad = AdamWorkspace(self.lib, self.dev)
-        self.warm = [int(self.scan.warmup), int(self.scan.warmup)]   # forward, backward
-        self._clean = [0, 0]
-        self._rep_host = torch.zeros(nat.CTL_WORDS, dtype=torch.int32).pin_memory()
-        self._rep_evt = None
-        self.timer = None       # optional KernelTimer (bench): per-call HIP events
-        self._tr = None
-        self._tr_c = None
-        self._invz = None
-        self.dense = False          # transition held by the dense log-domain scans
-        self.ws_dense = None
-        self.log_alpha = None       # (T, 2, L) f64 log filter state (dense scans)
-        self.ll64 = None            # (T, L) f64 unsplit ll (dense scans; None: not written)
-        self.alpha_bits = 0         # phase bits of the last forward (PHASE_NO_JUMP_ROWS or 0)
-        # device-side adaptive warm-up across the E-steps of ONE fit (run_em sets it; a
-        # decode is a single E-step whose result must not depend on earlier calls)
-        self.adaptive = False
-        self.ma_latent = None
-        # Gaussian observation model (GaussianGPLVMJump1D): when noise_std is set, the
-        # emission, tuning and M-step dispatch to gaussian.hip; the scans are shared.
-        self.noise_std = None
-        self.gauss_prior_std = 1.0
-        self._gstatus = None
-        self._ws_gm = None
+
+def suffstats_workspace_bytes(lib, sp, T, LA, planes):
+    """Workspace of the statistics kernels that spikes sp can reach for a (T, LA) P
+    (planes: pmg_suffstats_bf16x3 among them)."""
+    if sp.ybt is None:
+        return int(lib.pmg_suffstats_workspace_size(T, LA, sp.Np))
+    return int(max(lib.pmg_suffstats_bf16_workspace_size(T, LA, sp.N),
+                   lib.pmg_suffstats_bf16x3_workspace_size(T, LA, sp.N) if planes else 0))
+
+
+class EngineBase:
+    """What DeviceEM (R = 1) and RestartBatchEM (R restarts' latents stacked side by side)
+    share: the buffers at the stacked width R L, the banded transition, P and its bf16
+    planes, and the one Python call site of each native scan, statistics and emission
+    entry (argument order: include/pmg.h)."""
 
     # P as three bf16 planes between the backward and the statistics: bit-identical
     # statistics, measured slower at C3 (6 B written per cell instead of 4: k_backward
     # 180 -> 195 us, statistics 169 -> 176 us), so off by default
     PLANES = False
+    R = 1
+    dense = False
+    noise_std = None            # Poisson observation model unless DeviceEM is told otherwise
+    ll64 = None                 # no f64 ll unless DeviceEM holds a dense transition
+
+    def _alloc_buffers(self, mref_shape, alpha_shape, logc_shape):
+        """The buffers of both engines at the stacked width R L (after C, Cb are set); each
+        sequence has its own row reference, alpha and logc, in the engine's own layout."""
+        T, N, R, dev, sp = self.T, self.N, self.R, self.dev, self.sp
+        self.nblk = _ru(self.L, 32) // 32
+        LA, nb = R * self.L, R * self.nblk
+        f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+        self.delta = torch.empty((T, LA), dtype=f32, device=dev)
+        self.rblk = torch.empty((T, nb), dtype=f64, device=dev)
+        self.phi = torch.empty((T, nb), dtype=f32, device=dev)
+        self.mref = torch.empty(mref_shape, dtype=f64, device=dev)
+        self.alpha = torch.empty(alpha_shape, dtype=f32, device=dev)
+        self.logc = torch.empty(logc_shape, dtype=f64, device=dev)
+        self._P = torch.empty((T, LA), dtype=f32, device=dev)
+        # integer spikes: the backward writes P as its three exact bf16 planes, the operands
+        # of the statistics GEMMs (PMG_PHASE_P_BF16X3), instead of f32 P
+        self.use_planes = bool(self.PLANES and sp.ybt is not None and planes_ok(T, LA))
+        self.Pq = torch.empty((3, T, LA), dtype=torch.int16, device=dev) if self.use_planes else None
+        self._p_fresh = 'f32'       # which of _P / Pq holds the current posterior marginal
+        self.tuning64 = torch.empty((LA, N), dtype=f64, device=dev)
+        self.tuning32 = torch.empty((LA, N), dtype=f32, device=dev)
+        self.yw = torch.empty((LA, N), dtype=f64, device=dev)
+        self.tw = torch.empty(LA, dtype=f64, device=dev)
+        # zero-filled once: it holds the emission's sticky range flag (include/pmg.h)
+        self.ws_em = torch.zeros(int(self.lib.pmg_emission_workspace_size(T, LA, N)), dtype=u8, device=dev)
+        self._em_flag = _flag_view(self.lib, self.ws_em, T, LA, N)
+        # zero-filled once (include/pmg.h): the scan kernels keep its control words zero
+        self.ws_fb = torch.zeros(int(self.lib.pmg_fwdbwd_batched_workspace_size(T, self.L, min(self.C, self.Cb), R)),
+                                 dtype=u8, device=dev)
+        self.ws_ss = torch.empty(suffstats_workspace_bytes(self.lib, sp, T, LA, self.use_planes), dtype=u8,
+                                 device=dev)
+        self.ws_ad = AdamWorkspace(self.lib, dev)
+        self.warm = [int(self.scan.warmup), int(self.scan.warmup)]   # forward, backward
 
     @property
     def P(self):
-        """(T, L) f32 posterior marginal sum_d gamma.  When the last backward wrote the bf16
+        """(T, R L) f32 posterior marginal sum_d gamma.  When the last backward wrote the bf16
         planes, they are recombined here, exactly ((hi + mid) + lo in f32).  The buffer is
         handed out for reading or writing, so the next M-step reads it, not the planes."""
         if self._p_fresh == 'planes':
@@ -354,17 +338,7 @@ class DeviceEM:
     def _tw_bits(self):
         return nat.PHASE_TWO_WAVES if self.scan.two_waves else 0
 
-    # ------------------------------------------------------------------ setup
-    def set_transition(self, tr):
-        if tr.L != self.L:
-            raise ValueError("transition size mismatch")
-        if isinstance(tr, DenseTransition):
-            self._set_dense(tr)
-            return
-        if self.L > 1024:
-            raise nat.NativeError(f"n_latent_bin={self.L}: the banded scans hold L <= 1024; pass a DenseTransition "
-                                  "(gp_kernel.make_transition / dense_transition)")
-        self.dense = False
+    def _set_banded(self, tr):
         self._tr = tr
         self._invz = torch.as_tensor(tr.invz, device=self.dev)
         c = nat.Transition()
@@ -376,6 +350,213 @@ class DeviceEM:
         A = tr.A.astype(np.float32)
         c.A[0], c.A[1], c.A[2], c.A[3] = float(A[0, 0]), float(A[0, 1]), float(A[1, 0]), float(A[1, 1])
         self._tr_c = c
+
+    def set_ma_latent(self, ma_latent):
+        """(L,) latent mask, the same for each of the R stacked latent sets (None, or no
+        zero in it: no mask)."""
+        if ma_latent is None:
+            self.ma_latent = None
+            return
+        m = np.asarray(ma_latent)
+        if m.shape != (self.L,):
+            raise ValueError(f"ma_latent must have shape ({self.L},)")
+        if np.all(m != 0):
+            self.ma_latent = None
+        else:
+            self.ma_latent = torch.as_tensor(np.tile((m != 0).astype(np.uint8), self.R), device=self.dev)
+
+    def emission_status(self):
+        """Raise if an integer-path emission since the last check met |log lam| >= 60
+        (outside the exact digit range; device read: syncs), then clear the flag."""
+        _check_emission_flag(self._em_flag)
+
+    # ------------------------------------------------ the native call sites
+    def _emission_call(self, sp, sh, dt):
+        """(delta, rblk) (and ll64 where the engine holds one) of the tuning at width R L."""
+        LA = self.R * self.L
+        if self.noise_std is not None:
+            nat.check(self.lib.pmg_emission_gaussian(nat.ptr(sp.y), nat.ptr(self.tuning64), nat.ptr(sp.ma),
+                                                     int(sp.ma_2d), nat.ptr(self.ma_latent), float(self.noise_std),
+                                                     float(dt), self.T, self.L, self.N, nat.ptr(self.delta),
+                                                     nat.ptr(self.rblk), nat.ptr(self.ll64), sh),
+                      "pmg_emission_gaussian")
+        elif sp.int_path:
+            ma1 = sp.ma if (sp.ma is not None and not sp.ma_2d) else None
+            nat.check(self.lib.pmg_emission_poisson(nat.ptr(sp.yq), nat.ptr(sp.gconst), nat.ptr(self.tuning64),
+                                                    nat.ptr(ma1), nat.ptr(self.ma_latent), float(dt), self.T,
+                                                    LA, self.N, sp.Kp, nat.ptr(self.delta),
+                                                    nat.ptr(self.rblk), nat.ptr(self.ll64), nat.ptr(self.ws_em),
+                                                    self.ws_em.numel(), sh), "pmg_emission_poisson")
+        else:
+            nat.check(self.lib.pmg_emission_poisson_f64(nat.ptr(sp.y), nat.ptr(sp.gconst), nat.ptr(self.tuning64),
+                                                        nat.ptr(sp.ma), int(sp.ma_2d), nat.ptr(self.ma_latent),
+                                                        float(dt), self.T, LA, self.N, nat.ptr(self.delta),
+                                                        nat.ptr(self.rblk), nat.ptr(self.ll64), nat.ptr(self.ws_em),
+                                                        self.ws_em.numel(), sh), "pmg_emission_poisson_f64")
+
+    def _rowref_call(self, rblk, R, scale, phi, mref, sh):
+        """phi, mref of rblk (T, R nblk): each of the R stacked latent sets its own row reference."""
+        if R == 1:
+            nat.check(self.lib.pmg_emission_rowref(nat.ptr(rblk), self.T, self.nblk, float(scale), nat.ptr(phi),
+                                                   nat.ptr(mref), sh), "pmg_emission_rowref")
+        else:
+            nat.check(self.lib.pmg_emission_rowref_batched(nat.ptr(rblk), self.T, R * self.nblk, R, float(scale),
+                                                           nat.ptr(phi), nat.ptr(mref), sh),
+                      "pmg_emission_rowref_batched")
+
+    def emission(self, likelihood_scale=1.0, dt=1.0):
+        sh = nat.stream_handle()
+        with self._t('emission'):
+            self._emission_call(self.sp, sh, dt)
+        with self._t('emission_rowref'):
+            self._rowref_call(self.rblk, self.R, likelihood_scale, self.phi, self.mref, sh)
+
+    def _scan_bufs(self):
+        return self.delta, self.phi, self.mref, self.alpha, self.logc, self.ws_fb
+
+    def _forward_call(self, bufs, R, chunk, warmup, scale, logz_out, passes):
+        """The banded forward on bufs = (delta, phi, mref, alpha, logc, workspace) of R stacked
+        sequences: one native call per (timer section, phase word) of passes, in order.  The
+        argument list is built once for them (an E-step's two calls differ in the phase word only)."""
+        delta, phi, mref, alpha, logc, ws = bufs
+        seq = (nat.ptr(delta), nat.ptr(phi), nat.ptr(mref), self.T)
+        rest = (ctypes.byref(self._tr_c), float(scale), chunk, int(warmup), float(self.scan.tol), nat.ptr(alpha),
+                nat.ptr(logc), nat.ptr(logz_out), nat.ptr(ws), ws.numel(), nat.stream_handle())
+        for section, phase in passes:
+            with self._t(section):
+                if R == 1:
+                    nat.check(self.lib.pmg_forward_filter_phase(*seq, *rest, phase), "pmg_forward_filter")
+                else:
+                    nat.check(self.lib.pmg_forward_filter_batched(*seq, R, *rest, phase),
+                              "pmg_forward_filter_batched")
+
+    def _backward_call(self, bufs, R, chunk, warmup, scale, P_out, gamma, rho, passes):
+        """The banded backward on bufs and passes as _forward_call takes them; P_out: the f32 P
+        or its planes.  Only the R == 1 entry takes rho."""
+        if R != 1 and rho is not None:
+            raise ValueError("rho is written for a single sequence only")
+        delta, phi, _, alpha, _, ws = bufs
+        seq = (nat.ptr(delta), nat.ptr(phi), nat.ptr(alpha), self.T)
+        rest = (ctypes.byref(self._tr_c), float(scale), chunk, int(warmup), float(self.scan.tol), nat.ptr(P_out),
+                nat.ptr(gamma))
+        end = (nat.ptr(ws), ws.numel(), nat.stream_handle())
+        for section, phase in passes:
+            with self._t(section):
+                if R == 1:
+                    nat.check(self.lib.pmg_backward_smoother_phase(*seq, *rest, nat.ptr(rho), *end, phase),
+                              "pmg_backward_smoother")
+                else:
+                    nat.check(self.lib.pmg_backward_smoother_batched(*seq, R, *rest, *end, phase),
+                              "pmg_backward_smoother_batched")
+
+    def _forward_passes(self, bufs, R, chunk, warmup, scale, logz_out, main_bits, repair_bits):
+        self._forward_call(bufs, R, chunk, warmup, scale, logz_out,
+                           (('forward_filter', 1 | main_bits),       # main chunk-parallel pass (k_forward)
+                            ('forward_repair', 2 | repair_bits)))    # verify / relaxation / logZ
+
+    def _backward_passes(self, scale, P_out, gamma, rho, bits):
+        self._backward_call(self._scan_bufs(), self.R, self.Cb, self.warm[1], scale, P_out, gamma, rho,
+                            (('backward_smoother', 1 | bits | self._tw_bits()),   # main pass (k_backward)
+                             ('backward_repair', 2 | bits | self._seg_bits())))   # verify / relaxation
+
+    def _dense_forward_call(self, scale, logz_out, phase):
+        """DeviceEM with a dense transition.  phase 3: main pass + verify + relaxation + logZ
+        (what pmg_dense_forward runs); 2: the re-verification of a time shard's carry."""
+        nat.check(self.lib.pmg_dense_forward_phase(
+            nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.ll64), nat.ptr(self.mref), self.T,
+            ctypes.byref(self._tr_d), float(scale), self.Cd, int(self.warm[0]), float(self.scan.tol),
+            nat.ptr(self.alpha), nat.ptr(self.log_alpha), nat.ptr(self.logc), nat.ptr(logz_out),
+            nat.ptr(self.ws_dense), self.ws_dense.numel(), nat.stream_handle(), phase), "pmg_dense_forward_phase")
+
+    def _dense_backward_call(self, scale, P_out, gamma, log_gamma, log_rho, phase):
+        """Phases as _dense_forward_call; the f32 rho output of the entry is never asked for."""
+        nat.check(self.lib.pmg_dense_backward_phase(
+            nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.ll64), nat.ptr(self.log_alpha), self.T,
+            ctypes.byref(self._tr_d), float(scale), self.Cd, int(self.warm[1]), float(self.scan.tol),
+            nat.ptr(P_out), nat.ptr(gamma), nat.ptr(log_gamma), None, nat.ptr(log_rho),
+            nat.ptr(self.ws_dense), self.ws_dense.numel(), nat.stream_handle(), phase), "pmg_dense_backward_phase")
+
+    def _suffstats_call(self, P, y, T, Tp, LA):
+        """y_w, t_w of T rows.  P: (T, LA) f32, or its (3, T, LA) bf16 planes; y: the bf16
+        spikes transposed (Np, Tp) (integer counts), or yext (T, Np) f32 (Tp unused)."""
+        N, Np = self.N, self.sp.Np
+        out = (nat.ptr(self.yw), nat.ptr(self.tw), nat.ptr(self.ws_ss), self.ws_ss.numel(), nat.stream_handle())
+        if P.dtype == torch.int16:
+            nat.check(self.lib.pmg_suffstats_bf16x3(nat.ptr(P), LA, nat.ptr(y), T, Tp, LA, N, Np, *out),
+                      "pmg_suffstats_bf16x3")
+        elif y.dtype == torch.int16:
+            nat.check(self.lib.pmg_suffstats_bf16(nat.ptr(P), nat.ptr(y), T, Tp, LA, N, Np, *out),
+                      "pmg_suffstats_bf16")
+        else:
+            nat.check(self.lib.pmg_suffstats(nat.ptr(P), nat.ptr(y), T, LA, N, Np, *out), "pmg_suffstats")
+
+    def _suffstats(self):
+        """The statistics of the whole posterior marginal, read from whichever of the planes
+        and the f32 P the last backward wrote."""
+        with self._t('suffstats'):
+            P = self.Pq if self._p_fresh == 'planes' else self.P
+            y = self.sp.ybt if self.sp.ybt is not None else self.sp.yext
+            self._suffstats_call(P, y, self.T, self.sp.Tp, self.R * self.L)
+
+
+class DeviceEM(EngineBase):
+    """One fit's device state: spikes, basis, transition, workspaces, buffers."""
+
+    def __init__(self, spikes: SpikeData, L: int, basis=None, scan: ScanConfig | None = None):
+        self.lib = nat.load()
+        self.sp = spikes
+        self.dev = spikes.device
+        self.T, self.N, self.L = spikes.T, spikes.N, int(L)
+        self.scan = scan or ScanConfig()
+        self.C = self.scan.chunk_for(self.T)
+        self.Cb = self.scan.chunk_bwd_for(self.T)
+        T, L, dev = self.T, self.L, self.dev
+        self.basis = None
+        if basis is not None:
+            b = np.ascontiguousarray(basis, dtype=np.float32)
+            if b.shape[0] != L:
+                raise ValueError("basis must have n_latent_bin rows")
+            self.NB = int(b.shape[1])
+            self.basis = torch.as_tensor(b, device=dev)
+        self._alloc_buffers(T, (T, 2, L), T)
+        if self.ws_fb.numel() == 0 and L <= 1024:
+            raise nat.NativeError(f"pmg_fwdbwd_workspace_size(T={T}, L={L}) returned 0")
+        # L > 1024: only the dense log-domain scans (set_transition refuses a banded one)
+        self._clean = [0, 0]
+        self._rep_host = torch.zeros(nat.CTL_WORDS, dtype=torch.int32).pin_memory()
+        self._rep_evt = None
+        self.timer = None       # optional KernelTimer (bench): per-call HIP events
+        self._tr = None
+        self._tr_c = None
+        self._invz = None
+        self.dense = False          # transition held by the dense log-domain scans
+        self.ws_dense = None
+        self.log_alpha = None       # (T, 2, L) f64 log filter state (dense scans)
+        self.ll64 = None            # (T, L) f64 unsplit ll (dense scans; None: not written)
+        self.alpha_bits = 0         # phase bits of the last forward (PHASE_NO_JUMP_ROWS or 0)
+        # device-side adaptive warm-up across the E-steps of ONE fit (run_em sets it; a
+        # decode is a single E-step whose result must not depend on earlier calls)
+        self.adaptive = False
+        self.ma_latent = None
+        # Gaussian observation model (GaussianGPLVMJump1D): when noise_std is set, the
+        # emission, tuning and M-step dispatch to gaussian.hip; the scans are shared.
+        self.noise_std = None
+        self.gauss_prior_std = 1.0
+        self._gstatus = None
+        self._ws_gm = None
+
+    # ------------------------------------------------------------------ setup
+    def set_transition(self, tr):
+        if tr.L != self.L:
+            raise ValueError("transition size mismatch")
+        if isinstance(tr, DenseTransition):
+            self._set_dense(tr)
+            return
+        if self.L > 1024:
+            raise nat.NativeError(f"n_latent_bin={self.L}: the banded scans hold L <= 1024; pass a DenseTransition "
+                                  "(gp_kernel.make_transition / dense_transition)")
+        self.dense = False
+        self._set_banded(tr)
 
     def _set_dense(self, tr: DenseTransition):
         """Dense log-domain scans (dense_scan.hip): logK0 and its transpose on the device."""
@@ -411,18 +592,6 @@ class DeviceEM:
         if self.ll64 is None:   # the emission writes the unsplit f64 ll for the dense scans
             self.ll64 = torch.empty((self.T, self.L), dtype=torch.float64, device=self.dev)
 
-    def set_ma_latent(self, ma_latent):
-        if ma_latent is None:
-            self.ma_latent = None
-            return
-        m = np.asarray(ma_latent)
-        if m.shape != (self.L,):
-            raise ValueError(f"ma_latent must have shape ({self.L},)")
-        if np.all(m != 0):
-            self.ma_latent = None
-        else:
-            self.ma_latent = torch.as_tensor((m != 0).astype(np.uint8), device=self.dev)
-
     def set_log_posterior(self, log_post):
         """P = exp(log_posterior) (T, L) for the first M-step (fit_tuning_helper.py:38)."""
         lp = torch.as_tensor(np.ascontiguousarray(log_post, dtype=np.float32), device=self.dev)
@@ -434,22 +603,7 @@ class DeviceEM:
     # ------------------------------------------------------------------ M-step
     def m_step(self, W, mu, nu, count, cfg: AdamConfig, stats_out, lh_out, eh_out):
         """Sufficient statistics of self.P, then the Adam loop; W/mu/nu/count in place."""
-        sh = nat.stream_handle()
-        with self._t('suffstats'):
-          if self._p_fresh == 'planes':
-            nat.check(self.lib.pmg_suffstats_bf16x3(nat.ptr(self.Pq), self.L, nat.ptr(self.sp.ybt), self.T,
-                                                    self.sp.Tp, self.L, self.N, self.sp.Np, nat.ptr(self.yw),
-                                                    nat.ptr(self.tw), nat.ptr(self.ws_ss), self.ws_ss.numel(), sh),
-                      "pmg_suffstats_bf16x3")
-          elif self.sp.ybt is not None:
-            nat.check(self.lib.pmg_suffstats_bf16(nat.ptr(self.P), nat.ptr(self.sp.ybt), self.T, self.sp.Tp,
-                                                  self.L, self.N, self.sp.Np, nat.ptr(self.yw), nat.ptr(self.tw),
-                                                  nat.ptr(self.ws_ss), self.ws_ss.numel(), sh),
-                      "pmg_suffstats_bf16")
-          else:
-            nat.check(self.lib.pmg_suffstats(nat.ptr(self.P), nat.ptr(self.sp.yext), self.T, self.L, self.N,
-                                             self.sp.Np, nat.ptr(self.yw), nat.ptr(self.tw),
-                                             nat.ptr(self.ws_ss), self.ws_ss.numel(), sh), "pmg_suffstats")
+        self._suffstats()
         if self.noise_std is not None:
             self.gaussian_m_step(W)
             return
@@ -628,14 +782,6 @@ class DeviceEM:
         self.tuning32.copy_(self.tuning64.to(torch.float32))
 
     # ------------------------------------------------------------------ E-step
-    def emission(self, likelihood_scale=1.0, dt=1.0):
-        sp, sh = self.sp, nat.stream_handle()
-        with self._t('emission'):
-          self._emission_call(sp, sh, dt)
-        with self._t('emission_rowref'):
-          nat.check(self.lib.pmg_emission_rowref(nat.ptr(self.rblk), self.T, self.nblk, float(likelihood_scale),
-                                                 nat.ptr(self.phi), nat.ptr(self.mref), sh), "pmg_emission_rowref")
-
     def emission_unmasked(self, dt=1.0):
         """The emission contraction without a latent mask into fresh (delta0, rblk0)
         buffers, to be masked per use by emission_from."""
@@ -661,8 +807,7 @@ class DeviceEM:
                                                         nat.ptr(ma_latent_u8), nat.ptr(self.delta),
                                                         nat.ptr(self.rblk), sh), "pmg_emission_latent_mask")
         with self._t('emission_rowref'):
-            nat.check(self.lib.pmg_emission_rowref(nat.ptr(self.rblk), self.T, self.nblk, float(likelihood_scale),
-                                                   nat.ptr(self.phi), nat.ptr(self.mref), sh), "pmg_emission_rowref")
+            self._rowref_call(self.rblk, 1, likelihood_scale, self.phi, self.mref, sh)
 
     # masks per batched forward launch (log-marginal passes; ~13 device bytes per (t, l) each)
     MASK_BATCH_MAX = 16
@@ -723,46 +868,18 @@ class DeviceEM:
                                                                 nat.ptr(b['rblk']), sh),
                       "pmg_emission_latent_mask_batched")
         with self._t('emission_rowref'):
-            nat.check(self.lib.pmg_emission_rowref_batched(nat.ptr(b['rblk']), T, R * nb, R, float(likelihood_scale),
-                                                           nat.ptr(b['phi']), nat.ptr(b['mref']), sh),
-                      "pmg_emission_rowref_batched")
-        # no alpha is written (PMG_PHASE_NO_ALPHA); the kernels only need a valid pointer
-        args = (nat.ptr(b['delta']), nat.ptr(b['phi']), nat.ptr(b['mref']), T, R, ctypes.byref(self._tr_c),
-                float(likelihood_scale), C, int(sc.warmup), float(sc.tol), nat.ptr(self.alpha),
-                nat.ptr(b['logc']), nat.ptr(logz_out), nat.ptr(b['ws']), b['ws'].numel(), sh)
-        with self._t('forward_filter'):
-            nat.check(self.lib.pmg_forward_filter_batched(*args, 1 | nat.PHASE_NO_ALPHA), "pmg_forward_filter_batched")
-        with self._t('forward_repair'):
-            nat.check(self.lib.pmg_forward_filter_batched(
-                *args, 2 | nat.PHASE_NO_ALPHA | nat.phase_segments(self.masked_segments())),
-                "pmg_forward_filter_batched")
-        w = b['ws']
-        slab = (w.numel() // R) & ~255 if R > 1 else w.numel()
-        views = [w[r * slab:r * slab + 4 * nat.CTL_WORDS].view(torch.int32) for r in range(R)]
+            self._rowref_call(b['rblk'], R, likelihood_scale, b['phi'], b['mref'], sh)
+        # no alpha is written (PMG_PHASE_NO_ALPHA); the kernels only need a valid pointer.  The
+        # warm-up is the configured one (not self.warm[0], which the host adaptation moves) and
+        # the adaptive bit is off, so a mask's logZ does not depend on earlier E-steps; the
+        # two-wave bit is not set either
+        na = nat.PHASE_NO_ALPHA
+        self._forward_passes((b['delta'], b['phi'], b['mref'], self.alpha, b['logc'], b['ws']), R, C, sc.warmup,
+                             likelihood_scale, logz_out, na, na | nat.phase_segments(self.masked_segments()))
+        views = [ctl_view(b['ws'], R, r) for r in range(R)]
         host = torch.stack(views).cpu().numpy()   # one read of every mask's sticky timeout words
         for r in range(R):
             _raise_on_timeout(views[r], host[r], "masked forward relaxation")
-
-    def _emission_call(self, sp, sh, dt):
-        if self.noise_std is not None:
-            nat.check(self.lib.pmg_emission_gaussian(nat.ptr(sp.y), nat.ptr(self.tuning64), nat.ptr(sp.ma),
-                                                     int(sp.ma_2d), nat.ptr(self.ma_latent), float(self.noise_std),
-                                                     float(dt), self.T, self.L, self.N, nat.ptr(self.delta),
-                                                     nat.ptr(self.rblk), nat.ptr(self.ll64), sh),
-                      "pmg_emission_gaussian")
-        elif sp.int_path:
-            ma1 = sp.ma if (sp.ma is not None and not sp.ma_2d) else None
-            nat.check(self.lib.pmg_emission_poisson(nat.ptr(sp.yq), nat.ptr(sp.gconst), nat.ptr(self.tuning64),
-                                                    nat.ptr(ma1), nat.ptr(self.ma_latent), float(dt), self.T,
-                                                    self.L, self.N, sp.Kp, nat.ptr(self.delta),
-                                                    nat.ptr(self.rblk), nat.ptr(self.ll64), nat.ptr(self.ws_em),
-                                                    self.ws_em.numel(), sh), "pmg_emission_poisson")
-        else:
-            nat.check(self.lib.pmg_emission_poisson_f64(nat.ptr(sp.y), nat.ptr(sp.gconst), nat.ptr(self.tuning64),
-                                                        nat.ptr(sp.ma), int(sp.ma_2d), nat.ptr(self.ma_latent),
-                                                        float(dt), self.T, self.L, self.N, nat.ptr(self.delta),
-                                                        nat.ptr(self.rblk), nat.ptr(self.ll64), nat.ptr(self.ws_em),
-                                                        self.ws_em.numel(), sh), "pmg_emission_poisson_f64")
 
     def _adapt_warmup(self):
         """Adaptive warm-up from the previous E-step's repair counters, read without a
@@ -788,20 +905,14 @@ class DeviceEM:
     def ctl_words(self):
         """The scans' int32 control words (device view; see fb_kernels.h kCtl*; the dense
         scans use the same layout in their own workspace)."""
-        ws = self.ws_dense if self.dense else self.ws_fb
-        return ws[:4 * nat.CTL_WORDS].view(torch.int32)
+        return ctl_view(self.ws_dense if self.dense else self.ws_fb, 1, 0)
 
     def reset_adaptive(self):
         """Start of a fit: forget the adaptive warm-up decisions of earlier E-steps (the
         kCtlWarm words of both directions)."""
-        w = self.ws_fb[:4 * nat.CTL_WORDS].view(torch.int32)
+        w = ctl_view(self.ws_fb, 1, 0)
         w[nat.CTL_FWD + nat.CTL_WARM] = 0
         w[nat.CTL_BWD + nat.CTL_WARM] = 0
-
-    def emission_status(self):
-        """Raise if an integer-path emission since the last check met |log lam| >= 60
-        (outside the exact digit range; device read: syncs), then clear the flag."""
-        _check_emission_flag(self._em_flag)
 
     def _snapshot_repairs(self):
         self._rep_host.copy_(self.ctl_words(), non_blocking=True)
@@ -813,58 +924,33 @@ class DeviceEM:
         them from per-step scalars; callers that read only P / logZ skip 4 T L bytes)."""
         if self.dense:
             with self._t('forward_filter'):      # main pass + verify + relaxation + logZ
-                nat.check(self.lib.pmg_dense_forward(
-                    nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.ll64), nat.ptr(self.mref), self.T,
-                    ctypes.byref(self._tr_d),
-                    float(likelihood_scale), self.Cd, int(self.warm[0]), float(self.scan.tol),
-                    nat.ptr(self.alpha), nat.ptr(self.log_alpha), nat.ptr(self.logc), nat.ptr(logz_out),
-                    nat.ptr(self.ws_dense), self.ws_dense.numel(), nat.stream_handle()), "pmg_dense_forward")
+                self._dense_forward_call(likelihood_scale, logz_out, 3)
             return
         self._adapt_warmup()
-        sc = self.scan
-        args = (nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.mref), self.T, ctypes.byref(self._tr_c),
-                float(likelihood_scale), self.C, int(self.warm[0]), float(sc.tol), nat.ptr(self.alpha),
-                nat.ptr(self.logc), nat.ptr(logz_out), nat.ptr(self.ws_fb), self.ws_fb.numel(),
-                nat.stream_handle())
         self.alpha_bits = 0 if keep_alpha else nat.PHASE_NO_JUMP_ROWS
-        ad = nat.PHASE_ADAPTIVE_WARMUP if (sc.device_adaptive and self.adaptive) else 0
-        with self._t('forward_filter'):          # main chunk-parallel pass (k_forward)
-            nat.check(self.lib.pmg_forward_filter_phase(*args, 1 | ad | self.alpha_bits | self._tw_bits()), "pmg_forward_filter")
-        with self._t('forward_repair'):          # verify / relaxation / logZ
-            nat.check(self.lib.pmg_forward_filter_phase(*args, 2 | ad | self.alpha_bits | self._seg_bits()),
-                      "pmg_forward_filter")
+        bits = self.alpha_bits | (nat.PHASE_ADAPTIVE_WARMUP if (self.scan.device_adaptive and self.adaptive) else 0)
+        self._forward_passes(self._scan_bufs(), 1, self.C, self.warm[0], likelihood_scale, logz_out,
+                             bits | self._tw_bits(), bits | self._seg_bits())
 
     def backward(self, likelihood_scale, P=True, gamma=None, rho=None, log_gamma=None):
         """rho: the joint partner; with the dense scans it is written as log(rho), f64
         (see joint_log)."""
         if self.dense:
             with self._t('backward_smoother'):
-                nat.check(self.lib.pmg_dense_backward(
-                    nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.ll64), nat.ptr(self.log_alpha), self.T,
-                    ctypes.byref(self._tr_d),
-                    float(likelihood_scale), self.Cd, int(self.warm[1]), float(self.scan.tol),
-                    nat.ptr(self._P) if P else None, nat.ptr(gamma), nat.ptr(log_gamma), None, nat.ptr(rho),
-                    nat.ptr(self.ws_dense), self.ws_dense.numel(), nat.stream_handle()), "pmg_dense_backward")
+                self._dense_backward_call(likelihood_scale, self._P if P else None, gamma, log_gamma, rho, 3)
             if P:
                 self._p_fresh = 'f32'
             return
         if log_gamma is not None:
             raise ValueError("log_gamma is produced by the dense scans only")
-        sc = self.scan
         planes = bool(P) and self.use_planes
-        pout = (nat.ptr(self.Pq) if planes else nat.ptr(self._P)) if P else None
-        args = (nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.alpha), self.T, ctypes.byref(self._tr_c),
-                float(likelihood_scale), self.Cb, int(self.warm[1]), float(sc.tol),
-                pout, nat.ptr(gamma), nat.ptr(rho), nat.ptr(self.ws_fb),
-                self.ws_fb.numel(), nat.stream_handle())
-        ad = (nat.PHASE_ADAPTIVE_WARMUP if (sc.device_adaptive and self.adaptive) else 0) | \
+        # the planes or _P itself, not the P property: that would recombine stale planes first
+        pout = (self.Pq if planes else self._P) if P else None
+        bits = (nat.PHASE_ADAPTIVE_WARMUP if (self.scan.device_adaptive and self.adaptive) else 0) | \
             (nat.PHASE_P_BF16X3 if planes else 0)
         if P:
             self._p_fresh = 'planes' if planes else 'f32'
-        with self._t('backward_smoother'):       # main chunk-parallel pass (k_backward)
-            nat.check(self.lib.pmg_backward_smoother_phase(*args, 1 | ad | self._tw_bits()), "pmg_backward_smoother")
-        with self._t('backward_repair'):         # verify / relaxation
-            nat.check(self.lib.pmg_backward_smoother_phase(*args, 2 | ad | self._seg_bits()), "pmg_backward_smoother")
+        self._backward_passes(likelihood_scale, pout, gamma, rho, bits)
 
     def _need_banded(self, what):
         if self.dense or self._tr_c is None:
@@ -1154,7 +1240,7 @@ def posterior_outputs(gamma: torch.Tensor, log: bool = True):
     return lg, plm, pdm
 
 
-class RestartBatchEM:
+class RestartBatchEM(EngineBase):
     """R independent EM restarts of one recording on one GPU (model_selection_helper.py:53-59:
     the restarts differ only in their posterior init; SURVEY 8(e): 8 restarts per GPU at C5).
 
@@ -1195,69 +1281,27 @@ class RestartBatchEM:
             raise ValueError("basis must have n_latent_bin rows")
         self.NB = int(b.shape[1])
         self.basis = torch.as_tensor(b, device=dev)
-        LA = R * L
-        self.nblk = L // 32
-        f32, f64 = torch.float32, torch.float64
-        self.delta = torch.empty((T, LA), dtype=f32, device=dev)
-        self.rblk = torch.empty((T, R * self.nblk), dtype=f64, device=dev)
-        self.phi = torch.empty((T, R * self.nblk), dtype=f32, device=dev)
-        self.mref = torch.empty((T, R), dtype=f64, device=dev)
-        self.alpha = torch.empty((R, T, 2, L), dtype=f32, device=dev)
-        self.logc = torch.empty((R, T), dtype=f64, device=dev)
-        self._P = torch.empty((T, LA), dtype=f32, device=dev)
-        # as DeviceEM: P as its exact bf16 planes between the backward and the statistics.
-        # The gate here is the stacked width R L, a lone restart's is L, so near the 2 GiB
+        # P as its exact bf16 planes between the backward and the statistics (PLANES):
+        # the gate here is the stacked width R L, a lone restart's is L, so near the 2 GiB
         # plane bound a batch can take the f32-P path where the lone restart takes the
         # planes.  The two paths give y_w bit for bit (the planes are the exact split of
         # the same f32 P that k_ptb3 splits in-kernel) and t_w to ~1e-8 (f32 group sums over
         # different time groupings; test_backward_planes_bit_identical,
         # test_suffstats_vs_numpy), inside the restart-equivalence bar of 1e-6
         # (tests/test_gpu_restarts.py).  PLANES is off by default in both engines.
-        self.use_planes = bool(self.PLANES and spikes.ybt is not None and planes_ok(T, LA))
-        self.Pq = torch.empty((3, T, LA), dtype=torch.int16, device=dev) if self.use_planes else None
-        self._p_fresh = 'f32'
-        self.tuning64 = torch.empty((LA, N), dtype=f64, device=dev)
-        self.tuning32 = torch.empty((LA, N), dtype=f32, device=dev)
-        self.yw = torch.empty((LA, N), dtype=f64, device=dev)
-        self.tw = torch.empty(LA, dtype=f64, device=dev)
-        self.ws_em = torch.zeros(int(self.lib.pmg_emission_workspace_size(T, LA, N)), dtype=torch.uint8, device=dev)
-        self._em_flag = _flag_view(self.lib, self.ws_em, T, LA, N)
-        fb = int(self.lib.pmg_fwdbwd_batched_workspace_size(T, L, min(self.C, self.Cb), R))
-        if fb == 0:
+        self._alloc_buffers((T, R), (R, T, 2, L), (R, T))
+        if self.ws_fb.numel() == 0:
             raise nat.NativeError(f"n_latent_bin={L} unsupported by the scan kernels (max 1024)")
-        self.ws_fb = torch.zeros(fb, dtype=torch.uint8, device=dev)    # zero-filled once (include/pmg.h)
-        self.slab = (fb // R) & ~255 if R > 1 else fb
-        ss_bytes = (max(self.lib.pmg_suffstats_bf16_workspace_size(T, LA, N),
-                        self.lib.pmg_suffstats_bf16x3_workspace_size(T, LA, N) if self.use_planes else 0)
-                    if spikes.ybt is not None
-                    else self.lib.pmg_suffstats_workspace_size(T, LA, spikes.Np))
-        self.ws_ss = torch.empty(int(ss_bytes), dtype=torch.uint8, device=dev)
-        self.ws_ad = AdamWorkspace(self.lib, self.dev)
-        self.warm = [int(self.scan.warmup), int(self.scan.warmup)]
         self.timer = None
         self._tr_c = None
         self.ma_latent = None
 
-    _t = DeviceEM._t
-    _seg_bits = DeviceEM._seg_bits
-    _tw_bits = DeviceEM._tw_bits
-    PLANES = False
-    P = DeviceEM.P
-
     def set_transition(self, tr):
         if isinstance(tr, DenseTransition):
             raise NotImplementedError("batched restarts run the banded scans only")
-        DeviceEM.set_transition(self, tr)
-
-    def set_ma_latent(self, ma_latent):
-        if ma_latent is None:
-            self.ma_latent = None
-            return
-        m = np.asarray(ma_latent)
-        if m.shape != (self.L,):
-            raise ValueError(f"ma_latent must have shape ({self.L},)")
-        self.ma_latent = None if np.all(m != 0) else torch.as_tensor(
-            np.tile((m != 0).astype(np.uint8), self.R), device=self.dev)
+        if tr.L != self.L:
+            raise ValueError("transition size mismatch")
+        self._set_banded(tr)
 
     def set_log_posterior(self, log_posts):
         """P[:, r L:(r+1) L] = exp(log_posts[r]) for the first M-step; log_posts (R, T, L)."""
@@ -1272,23 +1316,8 @@ class RestartBatchEM:
     # ------------------------------------------------------------------ M-step
     def m_step(self, W, mu, nu, count, cfg: AdamConfig, stats_out, lh_out, eh_out):
         """W, mu, nu (R, NB, N) f64, count (R,) int64; stats_out (R, 4), lh/eh (R, maxiter)."""
-        sh = nat.stream_handle()
-        T, LA, N = self.T, self.R * self.L, self.N
-        with self._t('suffstats'):
-            if self._p_fresh == 'planes':
-                nat.check(self.lib.pmg_suffstats_bf16x3(nat.ptr(self.Pq), LA, nat.ptr(self.sp.ybt), T, self.sp.Tp,
-                                                        LA, N, self.sp.Np, nat.ptr(self.yw), nat.ptr(self.tw),
-                                                        nat.ptr(self.ws_ss), self.ws_ss.numel(), sh),
-                          "pmg_suffstats_bf16x3")
-            elif self.sp.ybt is not None:
-                nat.check(self.lib.pmg_suffstats_bf16(nat.ptr(self.P), nat.ptr(self.sp.ybt), T, self.sp.Tp, LA, N,
-                                                      self.sp.Np, nat.ptr(self.yw), nat.ptr(self.tw),
-                                                      nat.ptr(self.ws_ss), self.ws_ss.numel(), sh),
-                          "pmg_suffstats_bf16")
-            else:
-                nat.check(self.lib.pmg_suffstats(nat.ptr(self.P), nat.ptr(self.sp.yext), T, LA, N, self.sp.Np,
-                                                 nat.ptr(self.yw), nat.ptr(self.tw), nat.ptr(self.ws_ss),
-                                                 self.ws_ss.numel(), sh), "pmg_suffstats")
+        self._suffstats()
+        sh, N = nat.stream_handle(), self.N
         L, NB, R = self.L, self.NB, self.R
         batched = (L <= DeviceEM.PERSISTENT_MAX_L and NB <= DeviceEM.PERSISTENT_MAX_NB
                    and bool(self.lib.pmg_mstep_adam_batched_supported(L, NB, N, R)))
@@ -1325,67 +1354,29 @@ class RestartBatchEM:
                                                            nat.stream_handle()), "pmg_tuning_softplus_batched")
 
     # ------------------------------------------------------------------ E-step
-    def emission(self, likelihood_scale=1.0):
-        sp, sh = self.sp, nat.stream_handle()
-        T, LA, N = self.T, self.R * self.L, self.N
-        with self._t('emission'):
-            if sp.int_path:
-                ma1 = sp.ma if (sp.ma is not None and not sp.ma_2d) else None
-                nat.check(self.lib.pmg_emission_poisson(nat.ptr(sp.yq), nat.ptr(sp.gconst), nat.ptr(self.tuning64),
-                                                        nat.ptr(ma1), nat.ptr(self.ma_latent), 1.0, T, LA, N, sp.Kp,
-                                                        nat.ptr(self.delta), nat.ptr(self.rblk), None, nat.ptr(self.ws_em),
-                                                        self.ws_em.numel(), sh), "pmg_emission_poisson")
-            else:
-                nat.check(self.lib.pmg_emission_poisson_f64(nat.ptr(sp.y), nat.ptr(sp.gconst), nat.ptr(self.tuning64),
-                                                            nat.ptr(sp.ma), int(sp.ma_2d), nat.ptr(self.ma_latent),
-                                                            1.0, T, LA, N, nat.ptr(self.delta), nat.ptr(self.rblk),
-                                                            None, nat.ptr(self.ws_em), self.ws_em.numel(), sh),
-                          "pmg_emission_poisson_f64")
-        with self._t('emission_rowref'):
-            nat.check(self.lib.pmg_emission_rowref_batched(nat.ptr(self.rblk), T, self.R * self.nblk, self.R,
-                                                           float(likelihood_scale), nat.ptr(self.phi),
-                                                           nat.ptr(self.mref), sh), "pmg_emission_rowref_batched")
-
+    # emission(): the base's, at width R L (dt = 1, no ll64)
     def forward(self, likelihood_scale, logz_out, keep_alpha=True):
         """logz_out: (R,) f64 device tensor."""
         bits = (0 if keep_alpha else nat.PHASE_NO_JUMP_ROWS) | (nat.PHASE_ADAPTIVE_WARMUP if self.scan.device_adaptive
                                                                   else 0)   # RestartBatchEM: always one fit
-        args = (nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.mref), self.T, self.R,
-                ctypes.byref(self._tr_c), float(likelihood_scale), self.C, int(self.warm[0]), float(self.scan.tol),
-                nat.ptr(self.alpha), nat.ptr(self.logc), nat.ptr(logz_out), nat.ptr(self.ws_fb),
-                self.ws_fb.numel(), nat.stream_handle())
-        with self._t('forward_filter'):
-            nat.check(self.lib.pmg_forward_filter_batched(*args, 1 | bits | self._tw_bits()), "pmg_forward_filter_batched")
-        with self._t('forward_repair'):
-            nat.check(self.lib.pmg_forward_filter_batched(*args, 2 | bits | self._seg_bits()),
-                      "pmg_forward_filter_batched")
+        self._forward_passes(self._scan_bufs(), self.R, self.C, self.warm[0], likelihood_scale, logz_out,
+                             bits | self._tw_bits(), bits | self._seg_bits())
 
     def backward(self, likelihood_scale, gamma=None):
         """gamma: optional (R, T, 2, L) f32 posterior output."""
         planes = self.use_planes
-        args = (nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.alpha), self.T, self.R,
-                ctypes.byref(self._tr_c), float(likelihood_scale), self.Cb, int(self.warm[1]), float(self.scan.tol),
-                nat.ptr(self.Pq) if planes else nat.ptr(self._P), nat.ptr(gamma), nat.ptr(self.ws_fb),
-                self.ws_fb.numel(), nat.stream_handle())
-        ad = (nat.PHASE_ADAPTIVE_WARMUP if self.scan.device_adaptive else 0) | (nat.PHASE_P_BF16X3 if planes else 0)
+        bits = (nat.PHASE_ADAPTIVE_WARMUP if self.scan.device_adaptive else 0) | (nat.PHASE_P_BF16X3 if planes else 0)
         self._p_fresh = 'planes' if planes else 'f32'
-        with self._t('backward_smoother'):
-            nat.check(self.lib.pmg_backward_smoother_batched(*args, 1 | ad | self._tw_bits()), "pmg_backward_smoother_batched")
-        with self._t('backward_repair'):
-            nat.check(self.lib.pmg_backward_smoother_batched(*args, 2 | ad | self._seg_bits()),
-                      "pmg_backward_smoother_batched")
+        self._backward_passes(likelihood_scale, self.Pq if planes else self._P, gamma, None, bits)
 
     def e_step(self, likelihood_scale, logz_out, gamma=None):
         self.emission(likelihood_scale)
         self.forward(likelihood_scale, logz_out, keep_alpha=gamma is not None)
         self.backward(likelihood_scale, gamma)
 
-    def emission_status(self):
-        _check_emission_flag(self._em_flag)
-
     def ctl_words(self, r):
         """Restart r's scan control words (device view)."""
-        return self.ws_fb[r * self.slab:r * self.slab + 4 * nat.CTL_WORDS].view(torch.int32)
+        return ctl_view(self.ws_fb, self.R, r)
 
     def reset_adaptive(self):
         """Start of a fit: forget earlier adaptive warm-up decisions (every restart)."""

@@ -35,7 +35,6 @@ it is latency-bound on xGMI.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import time
 from dataclasses import dataclass
@@ -390,53 +389,31 @@ class ShardEM(DeviceEM):
         return self.ws_fb[off:off + 8 * self.Lpad].view(torch.float32)
 
     def suffstats_own(self):
-        lay, sh = self.lay, nat.stream_handle()
-        P = self.P[self.own]
+        """y_w, t_w over the shard's own rows of the f32 P."""
+        To, P = self.lay.T_own, self.P[self.own]
         with self._t('suffstats'):
             if self.ybt_own is not None:
-                nat.check(self.lib.pmg_suffstats_bf16(nat.ptr(P), nat.ptr(self.ybt_own), lay.T_own, self.Tp_own,
-                                                      self.L, self.N, self.sp.Np, nat.ptr(self.yw),
-                                                      nat.ptr(self.tw), nat.ptr(self.ws_ss), self.ws_ss.numel(),
-                                                      sh), "pmg_suffstats_bf16")
+                self._suffstats_call(P, self.ybt_own, To, self.Tp_own, self.L)
             else:
-                nat.check(self.lib.pmg_suffstats(nat.ptr(P), nat.ptr(self.sp.yext[self.own]), lay.T_own, self.L,
-                                                 self.N, self.sp.Np, nat.ptr(self.yw), nat.ptr(self.tw),
-                                                 nat.ptr(self.ws_ss), self.ws_ss.numel(), sh), "pmg_suffstats")
+                self._suffstats_call(P, self.sp.yext[self.own], To, 0, self.L)
 
+    # The carry calls re-run phase 2 without PMG_PHASE_ADAPTIVE_WARMUP: they leave the warm-up
+    # decision of the E-step's own passes unchanged (include/pmg.h).
     def forward_phase2(self, likelihood_scale, logz_scratch):
         if self.dense:
             with self._t('forward_carry'):
-                nat.check(self.lib.pmg_dense_forward_phase(
-                    nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.ll64), nat.ptr(self.mref), self.T,
-                    ctypes.byref(self._tr_d), float(likelihood_scale), self.Cd, int(self.warm[0]),
-                    float(self.scan.tol), nat.ptr(self.alpha), nat.ptr(self.log_alpha), nat.ptr(self.logc),
-                    nat.ptr(logz_scratch), nat.ptr(self.ws_dense), self.ws_dense.numel(), nat.stream_handle(), 2),
-                    "pmg_dense_forward_phase")
-            return
-        args = (nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.mref), self.T, ctypes.byref(self._tr_c),
-                float(likelihood_scale), self.C, int(self.warm[0]), float(self.scan.tol), nat.ptr(self.alpha),
-                nat.ptr(self.logc), nat.ptr(logz_scratch), nat.ptr(self.ws_fb), self.ws_fb.numel(),
-                nat.stream_handle())
-        with self._t('forward_carry'):
-            nat.check(self.lib.pmg_forward_filter_phase(*args, 2 | self.alpha_bits | self._seg_bits()),
-                      "pmg_forward_filter")
+                self._dense_forward_call(likelihood_scale, logz_scratch, 2)
+        else:
+            self._forward_call(self._scan_bufs(), 1, self.C, self.warm[0], likelihood_scale, logz_scratch,
+                               (('forward_carry', 2 | self.alpha_bits | self._seg_bits()),))
 
     def backward_phase2(self, likelihood_scale, P=True, gamma=None):
         if self.dense:
             with self._t('backward_carry'):
-                nat.check(self.lib.pmg_dense_backward_phase(
-                    nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.ll64), nat.ptr(self.log_alpha), self.T,
-                    ctypes.byref(self._tr_d), float(likelihood_scale), self.Cd, int(self.warm[1]),
-                    float(self.scan.tol), nat.ptr(self._P) if P else None, nat.ptr(gamma), None, None, None,
-                    nat.ptr(self.ws_dense), self.ws_dense.numel(), nat.stream_handle(), 2),
-                    "pmg_dense_backward_phase")
-            return
-        args = (nat.ptr(self.delta), nat.ptr(self.phi), nat.ptr(self.alpha), self.T, ctypes.byref(self._tr_c),
-                float(likelihood_scale), self.C, int(self.warm[1]), float(self.scan.tol),
-                nat.ptr(self.P) if P else None, nat.ptr(gamma), None, nat.ptr(self.ws_fb),
-                self.ws_fb.numel(), nat.stream_handle())
-        with self._t('backward_carry'):
-            nat.check(self.lib.pmg_backward_smoother_phase(*args, 2 | self._seg_bits()), "pmg_backward_smoother")
+                self._dense_backward_call(likelihood_scale, self._P if P else None, gamma, None, None, 2)
+        else:   # the P property (ShardEM never writes planes), and the forward chunk: one grid for both
+            self._backward_call(self._scan_bufs(), 1, self.C, self.warm[1], likelihood_scale,
+                                self.P if P else None, gamma, None, (('backward_carry', 2 | self._seg_bits()),))
 
     def repair_count(self):
         """(forward, backward) chunk-recompute counters (device tensor)."""

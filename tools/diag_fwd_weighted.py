@@ -7,7 +7,6 @@ Runs a C3 fit for n iterations, then, at the last one, the exact forward (verifi
 repaired) and backward with gamma, and speculative forward main passes with warm-ups W:
 for each, the fraction of chunk starts (s_in[c], the state at t_c - 1) further than tol
 from the exact alpha[t_c - 1], unweighted and gamma-weighted."""
-import ctypes
 import os
 import sys
 
@@ -75,10 +74,7 @@ def main():
     print(f"C3 after {n_it} EM iterations; {M - 1} forward boundaries, tol {eng.scan.tol:g}")
     alpha_save = eng.alpha.clone()
     for Wm in (2, 4, 8, 12, 16, 24, 32, 48):
-        args = (nat.ptr(eng.delta), nat.ptr(eng.phi), nat.ptr(eng.mref), T, ctypes.byref(eng._tr_c), 1.0, C, Wm,
-                float(eng.scan.tol), nat.ptr(eng.alpha), nat.ptr(eng.logc), nat.ptr(lz), nat.ptr(eng.ws_fb),
-                eng.ws_fb.numel(), nat.stream_handle())
-        nat.check(lib.pmg_forward_filter_phase(*args, 1), "fwd")
+        eng._forward_call(eng._scan_bufs(), 1, C, Wm, 1.0, lz, (('probe', 1),))
         torch.cuda.synchronize()
         spec = s_in[1:, :, :L].reshape(M - 1, 2 * L)
         du = hilbert_rows(spec, exact)

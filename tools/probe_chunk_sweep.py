@@ -4,7 +4,6 @@ After n EM iterations of a C3 fit, times the forward main pass (phase 1) with an
 its alpha stores, and the backward main pass, at chunk lengths C (M = T / C chains, one
 wave each), so the cost of the alpha write stream can be compared at 2 and 4 waves per
 SIMD (C = 49 / 25) -- the question behind splitting one chain over several waves."""
-import ctypes
 import json
 import os
 import sys
@@ -46,17 +45,13 @@ def main():
     res = {'n_it': n_it, 'C_default': eng.C, 'Cb_default': eng.Cb}
     ws = torch.zeros(int(lib.pmg_fwdbwd_workspace_size(T, L, 16)), dtype=torch.uint8, device=dev)
 
+    bufs = (eng.delta, eng.phi, eng.mref, eng.alpha, eng.logc, ws)    # the engine's, on a workspace for chunk 16
+
     def fwd(C, Wm, bits):
-        args = (nat.ptr(eng.delta), nat.ptr(eng.phi), nat.ptr(eng.mref), T, ctypes.byref(eng._tr_c), 1.0, C, Wm,
-                float(eng.scan.tol), nat.ptr(eng.alpha), nat.ptr(eng.logc), nat.ptr(lz), nat.ptr(ws),
-                ws.numel(), nat.stream_handle())
-        return lambda: nat.check(lib.pmg_forward_filter_phase(*args, 1 | bits), "fwd")
+        return lambda: eng._forward_call(bufs, 1, C, Wm, 1.0, lz, (('probe', 1 | bits),))
 
     def bwd(C, Wm):
-        args = (nat.ptr(eng.delta), nat.ptr(eng.phi), nat.ptr(eng.alpha), T, ctypes.byref(eng._tr_c), 1.0, C, Wm,
-                float(eng.scan.tol), nat.ptr(eng._P), None, None, nat.ptr(ws), ws.numel(),
-                nat.stream_handle())
-        return lambda: nat.check(lib.pmg_backward_smoother_phase(*args, 1), "bwd")
+        return lambda: eng._backward_call(bufs, 1, C, Wm, 1.0, eng._P, None, None, (('probe', 1),))
 
     for C in (25, 33, 49, 65, 98):
         for Wm in (0, 48):

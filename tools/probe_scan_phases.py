@@ -5,7 +5,6 @@ for several warm-ups, with and without the forward's alpha stores (PMG_PHASE_NO_
 measures the chip's streaming read / copy / triad bandwidth on buffers of the scan's size,
 so the output steps (read delta + write alpha, or read delta + alpha + write P) can be
 priced against the mixed read/write rate the HBM actually sustains."""
-import ctypes
 import json
 import os
 import sys
@@ -68,7 +67,6 @@ def main():
     eng.adaptive = True
     eng.set_transition(banded_transition(L, 1.0, 0.01, 0.01))
     eng.set_log_posterior(lp0)
-    lib = eng.lib
     W = torch.as_tensor(W0.astype(np.float64), device=dev).contiguous()
     mu, nu = torch.zeros_like(W), torch.zeros_like(W)
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -85,17 +83,13 @@ def main():
     C, Cb = eng.C, eng.Cb
     res['C'], res['Cb'] = C, Cb
 
+    bufs = eng._scan_bufs()
+
     def fwd(Wm, bits):
-        args = (nat.ptr(eng.delta), nat.ptr(eng.phi), nat.ptr(eng.mref), T, ctypes.byref(eng._tr_c), 1.0, C, Wm,
-                float(eng.scan.tol), nat.ptr(eng.alpha), nat.ptr(eng.logc), nat.ptr(lz), nat.ptr(eng.ws_fb),
-                eng.ws_fb.numel(), nat.stream_handle())
-        return lambda: nat.check(lib.pmg_forward_filter_phase(*args, 1 | bits), "fwd")
+        return lambda: eng._forward_call(bufs, 1, C, Wm, 1.0, lz, (('probe', 1 | bits),))
 
     def bwd(Wm):
-        args = (nat.ptr(eng.delta), nat.ptr(eng.phi), nat.ptr(eng.alpha), T, ctypes.byref(eng._tr_c), 1.0, Cb, Wm,
-                float(eng.scan.tol), nat.ptr(eng._P), None, None, nat.ptr(eng.ws_fb), eng.ws_fb.numel(),
-                nat.stream_handle())
-        return lambda: nat.check(lib.pmg_backward_smoother_phase(*args, 1), "bwd")
+        return lambda: eng._backward_call(bufs, 1, Cb, Wm, 1.0, eng._P, None, None, (('probe', 1),))
 
     for Wm in ((0, 48) if quick else (0, 8, 16, 32, 48, 96)):
         res[f'fwd_w{Wm}_us'] = 1e3 * timed(fwd(Wm, nat.PHASE_NO_JUMP_ROWS))
