@@ -474,6 +474,47 @@ int pmg_segment_sample(const float* alpha, int64_t T,
                        void* stream);
 
 /* ------------------------------------------------------------------ */
+/* Shuffle log marginals of many short, independent chains in one call:     */
+/* the forward filter's log marginal (decoder.filter_all_step,              */
+/* decoder.py:174-187) of every (segment, shuffle) pair, each shuffle       */
+/* re-reading the one emission the segment already has.  The reference       */
+/* decodes once per shuffle (reactivation_analysis.py,                       */
+/* circular_shuffle_spikes_within_epoch_and_decode); the two shuffles here   */
+/* need no new emission.  One wave per (segment, shuffle), banded           */
+/* transitions only.                                                         */
+/*   delta, phi, m, seg_off, order, tr, likelihood_scale: exactly as         */
+/*            pmg_segment_smoother takes them (segments clamped to           */
+/*            0 <= a <= b <= T on the device; workgroup b takes segment      */
+/*            order[b / R] (NULL: b / R) and shuffle b % R; `order` changes  */
+/*            scheduling only, entries outside 0 .. S-1 are skipped);        */
+/*   perm     (R,T) DEVICE int32, or NULL for the identity (time-bin         */
+/*            shuffle): step t of shuffle r of the segment owning row t      */
+/*            takes its emission row (delta, phi and m) from row perm[r,t].  */
+/*            The kernel clamps it into the segment's own [a, b), so no      */
+/*            access leaves the segment's rows;                              */
+/*   rot      (R,T) DEVICE int32, or NULL for none (column-cycle shuffle):   */
+/*            at step t the emission of latent l is the source row's         */
+/*            emission of latent (l + rot[r,t]) mod L, with that latent's    */
+/*            own block reference phi[src, ((l + rot) mod L) / 32].  The     */
+/*            kernel reduces rot into [0, L) itself, negative values         */
+/*            included, so no address leaves the row.                        */
+/* output:  logz (R,S) f64: logz[r,s] = the one-step predictive log          */
+/*          marginals of segment s filtered on shuffle r, summed in time     */
+/*          order, from the filters' own prior; an empty segment gets 0.     */
+/*          Nothing else is written.                                         */
+/* Contracts: with rot == NULL, logz[r,s] equals bit for bit the logz[s]     */
+/* pmg_segment_smoother writes on the rows of delta, phi and m gathered by   */
+/* perm[r] (perm == NULL: the true logz in every one of the R rows).  A      */
+/* value depends on its own segment's rows and its own perm[r] / rot[r]      */
+/* rows alone: not on the other segments, `order`, R, or the index r.        */
+/* No workspace.  PMG_EUNSUPPORTED for L > 1024.                             */
+int pmg_segment_shuffle_logz(const float* delta, const float* phi, const double* m, int64_t T,
+                             const int64_t* seg_off, int32_t S, const int32_t* order,
+                             const pmg_transition* tr, double likelihood_scale,
+                             const int32_t* perm, const int32_t* rot, int32_t R,
+                             double* logz, void* stream);
+
+/* ------------------------------------------------------------------ */
 /* Dense log-domain scans: any continuous kernel (custom_transition_kernel,  */
 /* gp_kernel.py:30-34 and 61-66; RBF kernels wider than PMG_MAX_BAND; the     */
 /* latent-only model of decoder_latentonly.py:33-224 with A = [[1,0],[1,0]]). */

@@ -613,6 +613,108 @@ class PoissonGPLVMJump1D:
         return {'sample_dynamics': r['sample_dynamics'], 'sample_latent': r['sample_latent'],
                 'log_marginal_final': float(r['log_marginal_final'][0])}
 
+    # shuffle_test_segments: device bytes of index arrays and random keys per launch, and the
+    # shuffles per random draw.  The draws are always made SHUFFLE_GEN_BLOCK shuffles at a time
+    # and a launch takes whole blocks, so the byte budget never changes a value.
+    SHUFFLE_BATCH_BYTES = 1 << 30
+    SHUFFLE_GEN_BLOCK = 32
+
+    def _shuffle_batch(self, n_rows, n_shuffle):
+        """Shuffles per launch: whole generation blocks within SHUFFLE_BATCH_BYTES (int32 perm
+        and rot, float64 keys and their int64 argsort per (shuffle, row)); at least one block."""
+        per = 24 * max(int(n_rows), 1)
+        g = int(self.SHUFFLE_GEN_BLOCK)
+        nb = max(1, min(-(-int(n_shuffle) // g), int(self.SHUFFLE_BATCH_BYTES) // (per * g)))
+        return nb * g
+
+    def shuffle_test_segments(self, y, segments=None, n_shuffle=1000, shuffle='time_bin', key=0, perm=None,
+                              rot=None, tuning=None, hyperparam={}, ma_neuron=None, ma_latent=None,
+                              likelihood_scale=1.):
+        """Is an event sequential beyond chance?  The forward filter's log marginal of every
+        event (ripple or replay candidate, trial, epoch) against n_shuffle shuffles of that
+        event, in one call.  The two standard replay shuffles re-read the event's own emission
+        (pmg_segment_shuffle_logz: one wave per (event, shuffle); the reference decodes once per
+        shuffle, reactivation_analysis.circular_shuffle_spikes_within_epoch_and_decode):
+          'time_bin'      the rows of an event are permuted in time;
+          'column_cycle'  each row's likelihood is rotated along the latent axis by a random
+                          amount, uniform on 0 .. n_latent_bin - 1;
+          'both'          a time-bin shuffle of column-cycled rows.
+        Each event is a chain of its own, started from the filters' own prior, as in
+        decode_latent_segments, and runs on the one-wave kernel whatever its length.  The true
+        score comes from the same launch as the shuffled ones (an identity row in front).
+
+        Inputs, gathering, defaults and hyper-parameter overrides as decode_latent_segments.
+        The random numbers are made on the device from a torch.Generator seeded with `key`: the
+        same key and inputs give the same result.  perm and / or rot: the caller's own shuffles,
+        (n_shuffle, Ttot) integer arrays or tensors with column = compact row, which replace the
+        generated ones (nothing is drawn then): step t of shuffle r takes the emission of
+        compact row perm[r, t], a permutation of each event's own rows, with its latents
+        rotated so that latent l reads latent (l + rot[r, t]) mod n_latent_bin.
+
+        Returns {'segment_offsets': (S + 1,) int64, 'log_marginal_final': (S,) float64,
+        'log_marginal_shuffle': (n_shuffle, S) float64, 'p_value': (S,) float64} with
+        p_value = shuffle_p_values(log_marginal_final, log_marginal_shuffle).  A transition that
+        needs the dense scans raises NotImplementedError; bad intervals, n_shuffle < 1, an
+        unknown `shuffle`, a perm or rot of the wrong shape or dtype, a perm row that is not a
+        permutation of each event's own rows, or a rotation together with a latent mask (it
+        would move masked bins) raise ValueError -- all before any device work."""
+        def check_args():
+            if int(n_shuffle) < 1 or int(n_shuffle) != n_shuffle:
+                raise ValueError(f"n_shuffle must be an integer >= 1, got {n_shuffle}")
+            if shuffle not in SHUFFLE_KINDS:
+                raise ValueError(f"shuffle must be one of {SHUFFLE_KINDS}, got {shuffle!r}")
+        hp, _, yc, off, ma, tuning, ma_latent = self._segments_prologue(
+            y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'shuffle_test_segments', check_args)
+        R, S, Ttot, L = int(n_shuffle), len(off) - 1, int(off[-1]), self.n_latent_bin
+        own = perm is not None or rot is not None
+        if perm is not None:
+            perm = _checked_shuffle_index(perm, 'perm', R, Ttot)
+            check_segment_permutations(perm, off)
+        if rot is not None:
+            rot = _checked_shuffle_index(rot, 'rot', R, Ttot)
+        use_perm = perm is not None if own else shuffle in ('time_bin', 'both')
+        use_rot = rot is not None if own else shuffle in ('column_cycle', 'both')
+        if use_rot and ma_latent is not None and not np.all(np.asarray(ma_latent).astype(bool)):
+            raise ValueError("shuffle_test_segments: a latent rotation would move the bins ma_latent masks")
+        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
+        dev = eng.dev
+        eng.emission(likelihood_scale)
+        off_d = torch.as_tensor(off, device=dev)
+        order_d = torch.as_tensor(segment_order(off), device=dev)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(key))
+        out = torch.empty((R + 1, S), dtype=torch.float64, device=dev)
+        ident = torch.arange(Ttot, dtype=torch.int32, device=dev)[None]
+        zero = torch.zeros((1, Ttot), dtype=torch.int32, device=dev)
+        nb, g = self._shuffle_batch(Ttot, R), int(self.SHUFFLE_GEN_BLOCK)
+        for r0 in range(0, R, nb):
+            r1 = min(R, r0 + nb)
+            if own:
+                p = perm[r0:r1].to(dev) if use_perm else None
+                q = rot[r0:r1].to(dev) if use_rot else None
+            else:      # drawn a block at a time, perm before rot: the same draws whatever nb
+                ps, qs = [], []
+                for b0 in range(r0, r1, g):
+                    n = min(g, r1 - b0)
+                    if use_perm:
+                        ps.append(segment_permutations(off, n, gen, dev))
+                    if use_rot:
+                        qs.append(torch.randint(0, L, (n, Ttot), generator=gen, dtype=torch.int32, device=dev))
+                p = torch.cat(ps) if use_perm else None
+                q = torch.cat(qs) if use_rot else None
+            if r0 == 0:   # the true score: the identity in front of the first launch
+                p = torch.cat([ident, p]) if use_perm else None
+                q = torch.cat([zero, q]) if use_rot else None
+            lo = r0 + (r0 > 0)
+            out[lo:r1 + 1] = eng.segment_shuffle_logz(likelihood_scale, off_d, order_d,
+                                                      perm=None if p is None else p.contiguous(),
+                                                      rot=None if q is None else q.contiguous())
+        eng.check_status()
+        out = _np(out)
+        true, shuf = np.ascontiguousarray(out[0]), np.ascontiguousarray(out[1:])
+        return {'segment_offsets': off, 'log_marginal_final': true, 'log_marginal_shuffle': shuf,
+                'p_value': shuffle_p_values(true, shuf)}
+
     def decode_latent_segments_viterbi(self, y, segments=None, tuning=None, hyperparam={}, ma_neuron=None,
                                        ma_latent=None, likelihood_scale=1.):
         """The jointly most likely (dynamics, latent) path of many independent events (ripple
@@ -1044,6 +1146,65 @@ def _checked_uniforms(uniforms, n_samples, n_rows):
     if not bool(((u >= 0) & (u < 1)).all()):
         raise ValueError("uniforms must lie in [0, 1)")
     return u
+
+
+SHUFFLE_KINDS = ('time_bin', 'column_cycle', 'both')
+
+
+def shuffle_p_values(true, shuffled):
+    """Monte-Carlo p-value of each event of shuffle_test_segments (host arrays): true (S,),
+    shuffled (n_shuffle, S); p[s] = (1 + #{r: shuffled[r, s] >= true[s]}) / (n_shuffle + 1),
+    a tie counting against the event (an event of one row under 'time_bin' gives 1)."""
+    true = np.asarray(true, np.float64)
+    shuffled = np.asarray(shuffled, np.float64)
+    if true.ndim != 1 or shuffled.ndim != 2 or shuffled.shape[1] != true.shape[0] or shuffled.shape[0] < 1:
+        raise ValueError(f"expected true (S,) and shuffled (n_shuffle >= 1, S), got {true.shape} and "
+                         f"{shuffled.shape}")
+    return (1.0 + np.sum(shuffled >= true[None, :], axis=0)) / (shuffled.shape[0] + 1.0)
+
+
+def _segment_ids(offsets, device):
+    """(Ttot,) int64 tensor: the segment of each compact row of CSR `offsets`."""
+    lens = torch.as_tensor(np.diff(np.asarray(offsets, np.int64)), device=device)
+    return torch.repeat_interleave(torch.arange(lens.numel(), device=device), lens)
+
+
+def segment_permutations(offsets, n_shuffle, generator=None, device=None):
+    """(n_shuffle, Ttot) int32 tensor on `device`: per row an independent uniform random
+    permutation of each segment's own compact rows (CSR `offsets`) -- the stable argsort along
+    the row axis of segment index + U[0, 1) in float64, drawn from `generator`."""
+    seg = _segment_ids(offsets, device)
+    keys = torch.rand((int(n_shuffle), seg.numel()), generator=generator, dtype=torch.float64, device=device)
+    keys += seg.to(torch.float64)[None, :]
+    return torch.argsort(keys, dim=1, stable=True).to(torch.int32)
+
+
+def _checked_shuffle_index(x, name, n_shuffle, n_rows):
+    """shuffle_test_segments' perm / rot as an int32 torch tensor (on whatever device it came
+    on): ValueError unless an integer (n_shuffle, n_rows) array whose values fit int32."""
+    x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
+        raise ValueError(f"{name} must hold integers, got {x.dtype}")
+    if tuple(x.shape) != (n_shuffle, n_rows):
+        raise ValueError(f"{name} must be (n_shuffle, n_rows) = {(n_shuffle, n_rows)}, got {tuple(x.shape)}")
+    if x.numel() and (int(x.min()) < -2 ** 31 or int(x.max()) > 2 ** 31 - 1):
+        raise ValueError(f"{name} must fit int32")
+    return x.to(torch.int32)
+
+
+def check_segment_permutations(perm, offsets):
+    """ValueError unless every row of perm (n_shuffle, Ttot) permutes each segment's own compact
+    rows (CSR `offsets`): every value a row of the column's segment, and none twice."""
+    perm = torch.as_tensor(perm).to(torch.int64)
+    seg = _segment_ids(offsets, perm.device)
+    n = seg.numel()
+    ok = bool(((perm >= 0) & (perm < n)).all())
+    if ok:
+        ok = bool((seg[perm] == seg[None, :]).all())
+    if ok:
+        ok = bool((torch.sort(perm, dim=1).values == torch.arange(n, device=perm.device)[None, :]).all())
+    if not ok:
+        raise ValueError("every row of perm must be a permutation of each segment's own rows")
 
 
 def _true_runs(mask):
@@ -1603,6 +1764,12 @@ class PoissonGPLVM1D(PoissonGPLVMJump1D):
         the banded linear-space filter's posteriors."""
         raise NotImplementedError(f"{type(self).__name__}.sample_latent_segments: the latent-only models need the "
                                   "dense log-domain scans, whose filter the path sampler does not read")
+
+    def shuffle_test_segments(self, y, segments=None, **kwargs):
+        """Not available, for the reason decode_latent_segments gives: the shuffle kernel runs
+        the banded linear-space filter."""
+        raise NotImplementedError(f"{type(self).__name__}.shuffle_test_segments: the latent-only models need the "
+                                  "dense log-domain scans, which the shuffle kernel does not run")
 
     def _dynamics_decode_args(self, hyperparam):
         hp = dict(hyperparam)

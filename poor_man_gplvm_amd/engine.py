@@ -1078,6 +1078,46 @@ class DeviceEM(EngineBase):
         sample_status_check(int(status.item()))
         return path_d, path_l
 
+    def segment_shuffle_logz(self, likelihood_scale, seg_off, order=None, perm=None, rot=None, n_shuffle=1,
+                             rows=None):
+        """Forward-filter log marginal of every (segment, shuffle) pair in one call
+        (pmg_segment_shuffle_logz: one wave per pair, re-reading the emission in place), after
+        emission() with the same likelihood_scale.  seg_off, order, rows: as segment_smoother
+        takes them.  perm (R, T) int32 device tensor or None: step t of shuffle r reads the
+        emission of row perm[r, t] (clamped into the step's own segment; None: its own row).
+        rot (R, T) int32 device tensor or None: the step's emission of latent l is the source
+        row's of latent (l + rot[r, t]) mod L.  R is the leading size of perm / rot, or
+        n_shuffle when both are None.  Returns logz (R, S) float64 on the device; nothing else
+        is written (alpha, logc stay as they were)."""
+        self._need_banded("segment_shuffle_logz")
+        r0, r1 = (0, self.T) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 < r1 <= self.T:
+            raise ValueError(f"rows {(r0, r1)} outside [0, {self.T}]")
+        T = r1 - r0
+        S = self._n_segments(seg_off, order)
+        R = None
+        for name, t in (('perm', perm), ('rot', rot)):
+            if t is None:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1
+                    or t.shape[1] != T or (R is not None and t.shape[0] != R)):
+                raise ValueError(f"{name} must be a (n_shuffle >= 1, {T}) int32 device tensor"
+                                 + (f" with n_shuffle = {R}" if R is not None else ""))
+            R = int(t.shape[0])
+        if R is None:
+            R = int(n_shuffle)
+            if R < 1:
+                raise ValueError("n_shuffle must be >= 1")
+        logz = torch.empty((R, S), dtype=torch.float64, device=self.dev)
+        with self._t('segment_shuffle_logz'):
+            nat.check(self.lib.pmg_segment_shuffle_logz(nat.ptr(self.delta[r0:r1]), nat.ptr(self.phi[r0:r1]),
+                                                        nat.ptr(self.mref[r0:r1]), T, nat.ptr(seg_off), S,
+                                                        nat.ptr(order), ctypes.byref(self._tr_c),
+                                                        float(likelihood_scale), nat.ptr(perm), nat.ptr(rot), R,
+                                                        nat.ptr(logz), nat.stream_handle()),
+                      "pmg_segment_shuffle_logz")
+        return logz
+
     def e_step(self, likelihood_scale, logz_out, gamma=None, rho=None, log_gamma=None, keep_alpha=None):
         """keep_alpha (default: whenever a posterior output is requested): write alpha in full."""
         if keep_alpha is None:

@@ -25,7 +25,17 @@ decode_latent_segments on the same events in the same process, the yardstick: th
 pays a backward pass and 2 L floats per row, the sampler R backward draws.  --parent-json: a
 record that the parent commit's tools/segments_bench.py wrote on the same machine, kept
 under "parent_commit".  Written to profiles/segments_sample_bench_c3.json.  No time is
-fixed: the ratio is reported as found."""
+fixed: the ratio is reported as found.
+
+--shuffle R [--shuffle-kind time_bin|column_cycle|both]: the same event set through
+shuffle_test_segments with R shuffles per event (wall time of every timed call, device time by
+section, the kernel's ns per filter step), next to a loop over the calls the project already
+has: per shuffle a row gather of delta / phi / m with torch, then segment_smoother forward only.
+The loop runs --loop-shuffles shuffles (default 50; fewer than R means a subset, scaled to R and
+flagged in the record), on the same shuffles as one segment_shuffle_logz call, and the largest
+difference between the two is recorded (0 for time_bin; a rotation's loop has to fold the block
+references into delta, so it differs by float32 rounding).  Written to
+profiles/segments_shuffle_bench_c3.json.  No ratio is fixed."""
 import argparse
 import json
 import os
@@ -177,6 +187,85 @@ def run_sample(args, y, tun):
     return rec
 
 
+def wall_all_ms(fn, calls, warmup):
+    """Every timed call's wall time (ms), for the spread."""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(1e3 * (time.perf_counter() - t0))
+    return out
+
+
+def run_shuffle(args, y, tun):
+    from poor_man_gplvm_amd.core import gather_segments, segment_order, segment_permutations
+    seg = event_intervals(args.events, y.shape[0])
+    R, kind = int(args.shuffle), args.shuffle_kind
+    m = model()
+    walls = wall_all_ms(lambda: m.shuffle_test_segments(y, seg, n_shuffle=R, shuffle=kind, key=0, tuning=tun),
+                        args.calls, args.warmup)
+    timer = KernelTimer()
+    mt = model(timer)
+    res = mt.shuffle_test_segments(y, seg, n_shuffle=R, shuffle=kind, key=0, tuning=tun)
+    kern = sections_ms(timer)
+    # the loop the project's other calls allow, over the same shuffles: per shuffle a row gather
+    # of delta / phi / m (a rotation needs the block references folded into delta first), then
+    # segment_smoother forward only
+    n_loop = min(R, int(args.loop_shuffles))
+    yc, off, ma = gather_segments(y, seg, None)
+    Ttot = int(off[-1])
+    eng = m._decode_engine(yc, tun, m._decode_hp({}), ma, m.ma_latent_default, exact=False)
+    dev = eng.dev
+    eng.emission(1.0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    perm = segment_permutations(off, n_loop, gen, dev) if kind != 'column_cycle' else None
+    rot = (torch.randint(0, L, (n_loop, Ttot), generator=gen, dtype=torch.int32, device=dev)
+           if kind != 'time_bin' else None)
+    off_d = torch.as_tensor(off, device=dev)
+    order_d = torch.as_tensor(segment_order(off), device=dev)
+    fused = eng.segment_shuffle_logz(1.0, off_d, order_d, perm=perm, rot=rot, n_shuffle=n_loop)
+    d0, p0, m0 = eng.delta.clone(), eng.phi.clone(), eng.mref.clone()
+    lat = torch.arange(L, device=dev)[None, :]
+    looped = torch.empty_like(fused)
+
+    def loop():
+        for r in range(n_loop):
+            idx = perm[r].long() if perm is not None else slice(None)
+            if rot is None:
+                eng.delta.copy_(d0[idx])
+                eng.phi.copy_(p0[idx])
+            else:
+                full = d0[idx] + torch.repeat_interleave(p0[idx], 32, dim=1)[:, :L]
+                eng.delta.copy_(torch.gather(full, 1, (lat + rot[r].long()[:, None]) % L))
+                eng.phi.zero_()
+            eng.mref.copy_(m0[idx])
+            looped[r] = eng.segment_smoother(1.0, off_d, order_d)[2]
+    loop_walls = wall_all_ms(loop, max(1, args.calls // 2), 1)
+    per_shuffle = min(loop_walls) / n_loop
+    diff = float((looped - fused).abs().max())
+    rel = float(((looped - fused).abs() / fused.abs()).max())
+    rows = int((seg[:, 1] - seg[:, 0]).sum())
+    k_ms = kern.get("segment_shuffle_logz", 0.0)
+    return {"shape": "c3", "N": N, "L": L, "events": int(len(seg)), "rows": rows, "n_shuffle": R,
+            "shuffle": kind, "mean_length": round(float((seg[:, 1] - seg[:, 0]).mean()), 2),
+            "shuffle_test_segments_wall_ms": round(min(walls), 3),
+            "shuffle_test_segments_wall_ms_all": [round(w, 3) for w in walls],
+            "shuffle_test_segments_kernel_ms": kern, "kernel_ms_total": round(sum(kern.values()), 4),
+            "segment_shuffle_logz_ns_per_step": round(1e6 * k_ms / (rows * (R + 1)), 4),
+            "loop_shuffles_timed": n_loop, "loop_is_a_subset_scaled_to_n_shuffle": bool(n_loop < R),
+            "loop_per_shuffle_wall_ms": round(per_shuffle, 4),
+            "loop_wall_ms_all": [round(w, 3) for w in loop_walls],
+            "loop_wall_ms_scaled": round(per_shuffle * R, 1),
+            "loop_over_one_call": round(per_shuffle * R / min(walls), 2),
+            "loop_vs_kernel_max_abs_diff": diff, "loop_vs_kernel_max_rel_diff": rel,
+            "p_value_min": float(res['p_value'].min()), "p_value_median": float(np.median(res['p_value']))}
+
+
 def run_crossover(args, y, tun):
     table, best = [], 0
     for n in CROSSOVER_LENGTHS:
@@ -208,6 +297,9 @@ def main():
     ap.add_argument("--crossover", action="store_true")
     ap.add_argument("--viterbi", action="store_true")
     ap.add_argument("--sample", type=int, default=0, metavar="R")
+    ap.add_argument("--shuffle", type=int, default=0, metavar="R")
+    ap.add_argument("--shuffle-kind", default="time_bin", choices=("time_bin", "column_cycle", "both"))
+    ap.add_argument("--loop-shuffles", type=int, default=50)
     ap.add_argument("--parent-json", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -217,6 +309,9 @@ def main():
     if args.crossover:
         rec = run_crossover(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_crossover_c3.json")
+    elif args.shuffle:
+        rec = run_shuffle(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_shuffle_bench_c3.json")
     elif args.sample:
         rec = run_sample(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_sample_bench_c3.json")
