@@ -514,6 +514,47 @@ int pmg_segment_shuffle_logz(const float* delta, const float* phi, const double*
                              const int32_t* perm, const int32_t* rot, int32_t R,
                              double* logz, void* stream);
 
+/* Per-neuron circular spike shuffles within events: the prepared spikes of  */
+/* R shuffled copies of the compact event rows, each neuron's spike train    */
+/* rolled circularly and independently within every event (np.roll along     */
+/* time; reactivation_analysis.py, circular_shuffle_column_independently).   */
+/* This is the shuffle that needs a new emission per copy: the outputs are   */
+/* exactly what pmg_emission_poisson / _f64 / pmg_emission_gaussian read,    */
+/* stacked copy after copy, so one emission call over R T rows and one       */
+/* pmg_segment_shuffle_logz call (perm = rot = NULL, R S segments) score     */
+/* every (shuffle, event) pair.                                              */
+/*   y        (T,N) DEVICE f32 compact rows, or NULL (the integer path);     */
+/*   yq       (>= T rows, Kp) DEVICE int8 as pmg_spikes_prepare wrote it,    */
+/*            or NULL;                                                       */
+/*   ma_neuron_1d  (N) DEVICE f32 0/1 mask, or NULL (all ones);              */
+/*   seg_off  (S+1) DEVICE int64 CSR rows, clamped to 0 <= a <= b <= T on    */
+/*            the device as pmg_segment_smoother clamps them;                */
+/*   shift    (R,S,N) DEVICE int32, any values: the kernel reduces them.     */
+/* outputs (each may be NULL, not all three):                                */
+/*   y_out      (R T, N) f32            (needs y);                           */
+/*   yq_out     (roundup(R T, 64), Kp) int8   (needs yq);                    */
+/*   gconst_out (R T) f64               (needs y or yq).                     */
+/* For shuffle r, segment s with clamped rows [a, b), len = b - a, row t in  */
+/* [a, b) and neuron n: k = shift[r,s,n] mod len taken into [0, len) (in     */
+/* 64-bit), src = a + ((t - a - k) mod len), and                             */
+/*   y_out[r T + t, n]  = y[src, n],                                         */
+/*   yq_out[r T + t, n] = yq[src, n], columns N .. Kp-1 zero,                */
+/*   gconst_out[r T + t] = sum_n ma[n] lgamma(y[src_n, n] + 1) (from the     */
+/*                        int8 values when y is NULL).                       */
+/* Rows that no clamped segment owns are not written, an empty segment       */
+/* writes nothing, and the padding rows R T .. roundup(R T, 64) - 1 of       */
+/* yq_out are zeroed.                                                        */
+/* Contract: for every row a segment owns, the three outputs equal bit for   */
+/* bit what pmg_spikes_prepare writes (yq, gconst, and y itself) for the     */
+/* host-rolled array with the same 1-D mask.  Every source row lies in its   */
+/* own segment's [a, b - 1] and every destination row below R T, whatever    */
+/* seg_off and shift hold.  No workspace, no atomics.                        */
+int pmg_segment_roll_prepare(const float* y, const int8_t* yq, const float* ma_neuron_1d,
+                             int64_t T, int32_t N, int32_t Kp,
+                             const int64_t* seg_off, int32_t S,
+                             const int32_t* shift, int32_t R,
+                             float* y_out, int8_t* yq_out, double* gconst_out, void* stream);
+
 /* ------------------------------------------------------------------ */
 /* Dense log-domain scans: any continuous kernel (custom_transition_kernel,  */
 /* gp_kernel.py:30-34 and 61-66; RBF kernels wider than PMG_MAX_BAND; the     */

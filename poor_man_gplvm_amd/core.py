@@ -299,6 +299,10 @@ class PoissonGPLVMJump1D:
         tr = self._scan_transition(mv, pmj, pjm, logK, logA, exact)
         self._check_latent_mask(tr, ma_latent)
         sp = SpikeData(y if isinstance(y, torch.Tensor) else np.asarray(y), ma)
+        return self._engine_on(sp, tuning, hyperparam, tr, ma_latent)
+
+    def _engine_on(self, sp, tuning, hyperparam, tr, ma_latent):
+        """A decode engine over the prepared spikes sp with the device transition tr."""
         eng = DeviceEM(sp, self.n_latent_bin, scan=self.scan_config)
         self._observation(eng, hyperparam)
         eng.set_transition(tr)
@@ -627,9 +631,83 @@ class PoissonGPLVMJump1D:
         nb = max(1, min(-(-int(n_shuffle) // g), int(self.SHUFFLE_BATCH_BYTES) // (per * g)))
         return nb * g
 
+    # shuffle='neuron_circular': device bytes of the stacked shuffled copies per launch (every
+    # buffer of the block engine per (shuffle, row), and the shifts), and the shuffles per random
+    # draw.  A launch takes whole generation blocks, so the byte budget never changes a value.
+    SHUFFLE_NEURON_BATCH_BYTES = 4 << 30
+    SHUFFLE_NEURON_GEN_BLOCK = 8
+    # the Poisson emissions read y off the integer path only; the Gaussian one always
+    _emission_reads_y = False
+
+    def _shuffle_neuron_batch(self, n_rows, n_seg, n_neuron, n_shuffle, with_y):
+        """Shuffles per launch of the per-neuron circular shuffle: whole generation blocks
+        within SHUFFLE_NEURON_BATCH_BYTES; at least one block.  Per (shuffle, row): delta, the
+        block references rblk and phi, m, yq and gconst (y where the emission reads it), and
+        the engine's alpha, P and logc, which the block engine allocates although the filter
+        never writes them; per shuffle: the float64 draws and the int32 shifts."""
+        L = self.n_latent_bin
+        nblk = -(-L // 32)
+        row = 4 * L + 12 * nblk + 8 + 128 * -(-int(n_neuron) // 128) + 8 + (4 * int(n_neuron) if with_y else 0)
+        row += 12 * L + 8
+        per = row * max(int(n_rows), 1) + 12 * int(n_seg) * int(n_neuron)
+        g = int(self.SHUFFLE_NEURON_GEN_BLOCK)
+        nb = max(1, min(-(-int(n_shuffle) // g), int(self.SHUFFLE_NEURON_BATCH_BYTES) // (per * g)))
+        return nb * g
+
+    def _shuffle_neuron_circular(self, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, n_shuffle, key,
+                                 shift, min_shift):
+        """shuffle_test_segments' per-neuron circular shuffle: (n_shuffle + 1, S) float64 host
+        array, the true (zero-shift) score in row 0.  The compact rows are uploaded and
+        prepared once; per launch, nb shuffled copies are made on the device
+        (pmg_segment_roll_prepare), one stacked emission serves them and every copy of every
+        event is a chain of its own in one segment_shuffle_logz call."""
+        R, S, Ttot, N = int(n_shuffle), len(off) - 1, int(off[-1]), int(yc.shape[1])
+        tr = self._scan_transition(hp.get('movement_variance', self.movement_variance),
+                                   hp.get('p_move_to_jump', self.p_move_to_jump),
+                                   hp.get('p_jump_to_move', self.p_jump_to_move), exact=False)
+        self._check_latent_mask(tr, ma_latent)
+        src = SpikeData(yc, None if ma is None else np.asarray(ma, np.float32))
+        dev = src.device
+        with_y = bool(self._emission_reads_y or not src.int_path)
+        g = int(self.SHUFFLE_NEURON_GEN_BLOCK)
+        nb = min(self._shuffle_neuron_batch(Ttot, S, N, R, with_y), -(-R // g) * g)
+        off_d = torch.as_tensor(off, device=dev)
+        # copy r of event s is segment r S + s of the stacked rows
+        stack = (np.arange(nb + 1, dtype=np.int64)[:, None] * Ttot + off[None, :-1]).reshape(-1)
+        stack = np.concatenate([stack, [(nb + 1) * Ttot]])
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(key))
+        out = torch.empty((R + 1, S), dtype=torch.float64, device=dev)
+        zero = torch.zeros((1, S, N), dtype=torch.int32, device=dev)
+        eng = None
+        for r0 in range(0, R, nb):
+            r1 = min(R, r0 + nb)
+            if shift is not None:
+                sh = shift[r0:r1].to(dev)
+            else:      # drawn a block at a time: the same draws whatever nb
+                sh = torch.cat([segment_neuron_shifts(off, min(g, r1 - b0), N, min_shift, gen, dev)
+                                for b0 in range(r0, r1, g)])
+            if r0 == 0:   # the true score: a zero-shift copy in front of the first launch
+                sh = torch.cat([zero, sh])
+            sh = sh.contiguous()
+            n = int(sh.shape[0])
+            if eng is None:
+                eng = self._engine_on(SpikeData.rolled(src, off_d, sh, n_copies=nb + 1, with_y=with_y), tuning, hp,
+                                      tr, ma_latent)
+            else:
+                eng.segment_roll_prepare(src, off_d, sh)
+            eng.emission(likelihood_scale)
+            so = stack[:n * S + 1]
+            lz = eng.segment_shuffle_logz(likelihood_scale, torch.as_tensor(so, device=dev),
+                                          torch.as_tensor(segment_order(so), device=dev), rows=(0, n * Ttot))
+            lo = r0 + (r0 > 0)
+            out[lo:r1 + 1] = lz.view(n, S)
+        eng.check_status()
+        return _np(out)
+
     def shuffle_test_segments(self, y, segments=None, n_shuffle=1000, shuffle='time_bin', key=0, perm=None,
                               rot=None, tuning=None, hyperparam={}, ma_neuron=None, ma_latent=None,
-                              likelihood_scale=1.):
+                              likelihood_scale=1., shift=None, min_shift=0):
         """Is an event sequential beyond chance?  The forward filter's log marginal of every
         event (ripple or replay candidate, trial, epoch) against n_shuffle shuffles of that
         event, in one call.  The two standard replay shuffles re-read the event's own emission
@@ -657,7 +735,23 @@ class PoissonGPLVMJump1D:
         needs the dense scans raises NotImplementedError; bad intervals, n_shuffle < 1, an
         unknown `shuffle`, a perm or rot of the wrong shape or dtype, a perm row that is not a
         permutation of each event's own rows, or a rotation together with a latent mask (it
-        would move masked bins) raise ValueError -- all before any device work."""
+        would move masked bins) raise ValueError -- all before any device work.
+
+        shuffle='neuron_circular' is the reference's own null
+        (circular_shuffle_column_independently): every neuron's spike train is rolled
+        circularly and independently within each event, which keeps each neuron's spike count
+        and autocorrelation inside the event and destroys only the between-neuron timing.
+        It needs a new emission per shuffle: the shuffled copies' prepared spikes are made on
+        the device from the one upload (pmg_segment_roll_prepare), SHUFFLE_NEURON_BATCH_BYTES
+        of stacked copies per launch, one emission serves a launch and every copy of every
+        event is a chain of its own.  The shifts of event s are uniform on lo .. hi - 1 with
+        lo = min_shift where the event has more than 2 min_shift rows, else 0, and hi = rows -
+        lo (segment_neuron_shifts; the reference's randint(min_shift, n_time - min_shift)).
+        shift: the caller's own shuffles, an (n_shuffle, S, n_neuron) integer array or tensor of
+        any values (np.roll's meaning; nothing is drawn then); it selects this shuffle whatever
+        `shuffle` says and cannot be combined with perm / rot.  A latent mask is fine; a 2-D
+        (per-time) ma_neuron, a shift of the wrong shape or dtype and min_shift < 0 raise
+        ValueError before any device work."""
         def check_args():
             if int(n_shuffle) < 1 or int(n_shuffle) != n_shuffle:
                 raise ValueError(f"n_shuffle must be an integer >= 1, got {n_shuffle}")
@@ -666,6 +760,22 @@ class PoissonGPLVMJump1D:
         hp, _, yc, off, ma, tuning, ma_latent = self._segments_prologue(
             y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'shuffle_test_segments', check_args)
         R, S, Ttot, L = int(n_shuffle), len(off) - 1, int(off[-1]), self.n_latent_bin
+        if shift is not None or shuffle == 'neuron_circular':
+            if perm is not None or rot is not None:
+                raise ValueError("shuffle_test_segments: shift (or shuffle='neuron_circular') cannot be combined "
+                                 "with perm / rot")
+            if ma is not None and np.ndim(ma) == 2:
+                raise ValueError("shuffle_test_segments: the per-neuron circular shuffle takes a 1-D ma_neuron "
+                                 "(a per-time mask would have to roll with the spikes)")
+            if int(min_shift) != min_shift or int(min_shift) < 0:
+                raise ValueError(f"min_shift must be an integer >= 0, got {min_shift}")
+            if shift is not None:
+                shift = _checked_neuron_shift(shift, R, S, int(yc.shape[1]))
+            out = self._shuffle_neuron_circular(yc, off, ma, tuning, hp, ma_latent, likelihood_scale, R, key,
+                                                shift, int(min_shift))
+            true, shuf = np.ascontiguousarray(out[0]), np.ascontiguousarray(out[1:])
+            return {'segment_offsets': off, 'log_marginal_final': true, 'log_marginal_shuffle': shuf,
+                    'p_value': shuffle_p_values(true, shuf)}
         own = perm is not None or rot is not None
         if perm is not None:
             perm = _checked_shuffle_index(perm, 'perm', R, Ttot)
@@ -1148,7 +1258,7 @@ def _checked_uniforms(uniforms, n_samples, n_rows):
     return u
 
 
-SHUFFLE_KINDS = ('time_bin', 'column_cycle', 'both')
+SHUFFLE_KINDS = ('time_bin', 'column_cycle', 'both', 'neuron_circular')
 
 
 def shuffle_p_values(true, shuffled):
@@ -1177,6 +1287,40 @@ def segment_permutations(offsets, n_shuffle, generator=None, device=None):
     keys = torch.rand((int(n_shuffle), seg.numel()), generator=generator, dtype=torch.float64, device=device)
     keys += seg.to(torch.float64)[None, :]
     return torch.argsort(keys, dim=1, stable=True).to(torch.int32)
+
+
+def segment_neuron_shifts(offsets, n_shuffle, n_neuron, min_shift=0, generator=None, device=None):
+    """(n_shuffle, S, n_neuron) int32 tensor on `device`: the per-neuron circular shifts of
+    shuffle_test_segments(shuffle='neuron_circular') for the events of CSR `offsets`.
+    shift = lo_s + floor(U (hi_s - lo_s)), clamped to hi_s - 1, with U uniform on [0, 1) in
+    float64 from `generator`, lo_s = min_shift where event s has more than 2 min_shift rows,
+    else 0, and hi_s = rows_s - lo_s: the reference's randint(min_shift, n_time - min_shift),
+    made well defined for short events."""
+    if int(min_shift) != min_shift or int(min_shift) < 0:
+        raise ValueError(f"min_shift must be an integer >= 0, got {min_shift}")
+    lens = np.diff(np.asarray(offsets, np.int64))
+    lo = np.where(lens > 2 * int(min_shift), int(min_shift), 0).astype(np.int64)
+    hi = lens - lo
+    lo_t = torch.as_tensor(lo, device=device)[None, :, None]
+    hi_t = torch.as_tensor(hi, device=device)[None, :, None]
+    u = torch.rand((int(n_shuffle), lens.size, int(n_neuron)), generator=generator, dtype=torch.float64,
+                   device=device)
+    s = lo_t + torch.floor(u * (hi_t - lo_t).to(torch.float64)).to(torch.int64)
+    return torch.minimum(s, hi_t - 1).to(torch.int32)
+
+
+def _checked_neuron_shift(x, n_shuffle, n_seg, n_neuron):
+    """shuffle_test_segments' shift as an int32 torch tensor (on whatever device it came on):
+    ValueError unless an integer (n_shuffle, S, n_neuron) array whose values fit int32."""
+    x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
+    if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
+        raise ValueError(f"shift must hold integers, got {x.dtype}")
+    want = (n_shuffle, n_seg, n_neuron)
+    if tuple(x.shape) != want:
+        raise ValueError(f"shift must be (n_shuffle, n_segment, n_neuron) = {want}, got {tuple(x.shape)}")
+    if x.numel() and (int(x.min()) < -2 ** 31 or int(x.max()) > 2 ** 31 - 1):
+        raise ValueError("shift must fit int32")
+    return x.to(torch.int32)
 
 
 def _checked_shuffle_index(x, name, n_shuffle, n_rows):
@@ -1588,6 +1732,8 @@ class GaussianGPLVMJump1D(PoissonGPLVMJump1D):
     analytic M-step (gaussian_m_step_analytic, fit_tuning_helper.py:44-61; no optimiser
     state).  Same jump dynamics, scans, sufficient statistics and result dicts as the
     Poisson model; the emission, tuning and M-step run in gaussian.hip."""
+
+    _emission_reads_y = True
 
     def __init__(self, n_neuron, noise_std=0.5, **kwargs):
         super().__init__(n_neuron, **kwargs)

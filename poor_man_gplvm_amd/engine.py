@@ -195,6 +195,62 @@ class SpikeData:
         if self.ybt is not None:
             self._transpose()
 
+    @classmethod
+    def rolled(cls, src, seg_off, shift, n_copies=None, with_y=None):
+        """The prepared spikes of stacked per-neuron circular shuffles of src's rows within
+        the segments of seg_off (pmg_segment_roll_prepare): copy r is rows r src.T ..
+        (r + 1) src.T - 1, neuron n of segment s rolled by shift[r, s, n] (np.roll along time).
+        seg_off (S + 1,) int64 and shift (n, S, N) int32 device tensors; n_copies >= n: the
+        copies the buffers hold (default n), for roll() to refill in place with up to as many.
+        Only what an emission reads is made: yq and gconst, and y when with_y (default: off
+        the integer path; the Gaussian emission reads y too) -- no yext, no bf16 transpose and
+        no flags sync.  flags, int_path, ma, Kp and Np are src's: a roll within a segment keeps
+        each neuron's multiset of counts (the argument refresh() makes).  Rows that no segment
+        owns are zero.  A per-time (2-D) mask would have to roll too: ValueError."""
+        if src.ma_2d:
+            raise ValueError("rolled spikes take a 1-D ma_neuron (a per-time mask would have to roll too)")
+        if not (isinstance(shift, torch.Tensor) and shift.dim() == 3):
+            raise ValueError("shift must be a (n_shuffle, S, N) int32 device tensor")
+        R = int(shift.shape[0] if n_copies is None else n_copies)
+        if R < max(1, int(shift.shape[0])):
+            raise ValueError(f"n_copies={n_copies} below the {int(shift.shape[0])} shuffles of shift")
+        sp = cls.__new__(cls)
+        sp.src_T = src.T
+        sp.T, sp.N, sp.device = R * src.T, src.N, src.device
+        sp.Kp, sp.Np, sp.Tp = src.Kp, src.Np, _ru(R * src.T, 64)
+        sp.ma, sp.ma_2d, sp.flags, sp.int_path = src.ma, False, src.flags, src.int_path
+        sp.yext = sp.ybt = None
+        dev = sp.device
+        with_y = (not src.int_path) if with_y is None else bool(with_y)
+        sp.y = torch.zeros((sp.T, sp.N), dtype=torch.float32, device=dev) if with_y else None
+        sp.yq = torch.zeros((sp.Tp, sp.Kp), dtype=torch.int8, device=dev)
+        sp.gconst = torch.zeros(sp.T, dtype=torch.float64, device=dev)
+        sp.roll(src, seg_off, shift)
+        return sp
+
+    def roll(self, src, seg_off, shift):
+        """Refill a rolled() SpikeData in place from the same src with other shifts: shift
+        (n, S, N) int32 rewrites copies 0 .. n - 1 (n at most the copies held); the copies
+        beyond keep their earlier rows.  Stays on the stream (no sync, no allocation)."""
+        T = getattr(self, 'src_T', None)
+        if T is None or T != src.T or self.N != src.N or self.Kp != src.Kp:
+            raise ValueError("roll() refills a SpikeData made by rolled() from the same source")
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.numel() < 1:
+            raise ValueError("seg_off must be a (S + 1,) int64 device tensor")
+        S = seg_off.numel() - 1
+        if (not isinstance(shift, torch.Tensor) or shift.dtype != torch.int32 or shift.dim() != 3
+                or shift.shape[0] < 1 or tuple(shift.shape[1:]) != (S, self.N)):
+            raise ValueError(f"shift must be a (n_shuffle >= 1, {S}, {self.N}) int32 device tensor")
+        n = int(shift.shape[0])
+        if n * T > self.T:
+            raise ValueError(f"{n} shuffles of {T} rows exceed the {self.T} rows held")
+        nat.check(nat.load().pmg_segment_roll_prepare(nat.ptr(src.y if self.y is not None or not src.int_path
+                                                              else None),
+                                                      nat.ptr(src.yq), nat.ptr(src.ma), T, self.N, self.Kp,
+                                                      nat.ptr(seg_off), S, nat.ptr(shift), n, nat.ptr(self.y),
+                                                      nat.ptr(self.yq), nat.ptr(self.gconst), nat.stream_handle()),
+                  "pmg_segment_roll_prepare")
+
 
 class KernelTimer:
     """Per-call HIP event pairs on the current stream (torch.cuda.Event records on
@@ -1117,6 +1173,13 @@ class DeviceEM(EngineBase):
                                                         nat.ptr(logz), nat.stream_handle()),
                       "pmg_segment_shuffle_logz")
         return logz
+
+    def segment_roll_prepare(self, src, seg_off, shift):
+        """Refill this engine's spikes -- a SpikeData.rolled() of src -- with the shuffles of
+        shift (n, S, N) (SpikeData.roll: pmg_segment_roll_prepare, on the stream); the next
+        emission() reads them."""
+        with self._t('segment_roll_prepare'):
+            self.sp.roll(src, seg_off, shift)
 
     def e_step(self, likelihood_scale, logz_out, gamma=None, rho=None, log_gamma=None, keep_alpha=None):
         """keep_alpha (default: whenever a posterior output is requested): write alpha in full."""

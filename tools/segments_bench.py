@@ -35,7 +35,17 @@ The loop runs --loop-shuffles shuffles (default 50; fewer than R means a subset,
 flagged in the record), on the same shuffles as one segment_shuffle_logz call, and the largest
 difference between the two is recorded (0 for time_bin; a rotation's loop has to fold the block
 references into delta, so it differs by float32 rounding).  Written to
-profiles/segments_shuffle_bench_c3.json.  No ratio is fixed."""
+profiles/segments_shuffle_bench_c3.json.  No ratio is fixed.
+
+--shuffle R --shuffle-kind neuron_circular: the per-neuron circular spike shuffle, which needs a
+new emission per shuffle.  Recorded: the one call (every timed call's wall time with min,
+median and max, device time by section); the only route without it, a loop of a host roll plus
+decode_latent_segments per shuffle, timed on --loop-shuffles shuffles (20 here) and scaled;
+and, for the roll kernel alone, the route it replaces on the same rows -- a segment-aware torch
+gather of f32 y into the stacked tensor, then SpikeData.refresh() -- with the two routes' yq and
+gconst compared bit for bit.  Device time per kernel comes from running this tool under
+rocprofv3 --kernel-trace --stats (--no-loop skips everything but the one call).  Written to
+profiles/segments_shuffle_bench_c3_neuron_circular.json.  No ratio is fixed."""
 import argparse
 import json
 import os
@@ -67,13 +77,13 @@ def model(timer=None, **scan):
     m = P.PoissonGPLVMJump1D(N, n_latent_bin=L, tuning_lengthscale=10., movement_variance=1.,
                              scan_config=ScanConfig(**scan))
     if timer is not None:       # every engine the decode builds reports to the timer
-        make = m._decode_engine
+        make = m._engine_on
 
         def with_timer(*a, **k):
             eng = make(*a, **k)
             eng.timer = timer
             return eng
-        m._decode_engine = with_timer
+        m._engine_on = with_timer
     return m
 
 
@@ -266,6 +276,104 @@ def run_shuffle(args, y, tun):
             "p_value_min": float(res['p_value'].min()), "p_value_median": float(np.median(res['p_value']))}
 
 
+def host_roll(yc, off, shift):
+    """roll_segments of the whole compact array at once: row t of event s takes row
+    a_s + (t - a_s - shift[s, n]) mod len_s of neuron n."""
+    lens = np.diff(off)
+    seg_of = np.repeat(np.arange(len(lens)), lens)
+    a, ln = off[:-1][seg_of][:, None], lens[seg_of][:, None]
+    rel = np.arange(int(off[-1]))[:, None] - a
+    return np.take_along_axis(yc, a + (rel - shift[seg_of]) % ln, axis=0)
+
+
+def run_neuron_shuffle(args, y, tun):
+    from poor_man_gplvm_amd.core import gather_segments, segment_neuron_shifts
+    from poor_man_gplvm_amd.engine import SpikeData
+    seg = event_intervals(args.events, y.shape[0])
+    R = int(args.shuffle)
+    m = model()
+    call = lambda: m.shuffle_test_segments(y, seg, n_shuffle=R, shuffle='neuron_circular', key=0, tuning=tun)  # noqa: E731
+    walls = wall_all_ms(call, args.calls, args.warmup)
+    rows = int((seg[:, 1] - seg[:, 0]).sum())
+    yc, off, _ = gather_segments(y, seg, None)
+    rec = {"shape": "c3", "N": N, "L": L, "events": int(len(seg)), "rows": rows, "n_shuffle": R,
+           "shuffle": "neuron_circular", "mean_length": round(float((seg[:, 1] - seg[:, 0]).mean()), 2),
+           "shuffles_per_launch": int(m._shuffle_neuron_batch(rows, len(seg), N, R, False)),
+           "shuffle_test_segments_wall_ms_all": [round(w, 3) for w in walls],
+           "shuffle_test_segments_wall_ms_min": round(min(walls), 3),
+           "shuffle_test_segments_wall_ms_median": round(float(np.median(walls)), 3),
+           "shuffle_test_segments_wall_ms_max": round(max(walls), 3),
+           "estimate_in_the_issue_ms_per_1000_shuffles": 100.0}
+    if args.no_loop:
+        return rec
+    timer = KernelTimer()
+    res = model(timer).shuffle_test_segments(y, seg, n_shuffle=R, shuffle='neuron_circular', key=0, tuning=tun)
+    kern = sections_ms(timer)
+    rec.update({"shuffle_test_segments_section_ms": kern, "section_ms_total": round(sum(kern.values()), 4),
+                "section_ms_per_shuffle": {k: round(v / (R + 1), 5) for k, v in kern.items()},
+                "p_value_min": float(res['p_value'].min()), "p_value_median": float(np.median(res['p_value']))})
+    # the only route without the kernel: per shuffle a host roll and a decode_latent_segments call
+    n_loop = min(R, int(args.loop_shuffles))
+    dev = torch.device('cuda', torch.cuda.current_device())
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    shift_d = segment_neuron_shifts(off, n_loop, N, 0, gen, dev)
+    shift = shift_d.cpu().numpy().astype(np.int64)
+    looped = np.empty((n_loop, len(seg)))
+
+    def loop():
+        for r in range(n_loop):
+            yr = host_roll(yc, off, shift[r])
+            looped[r] = m.decode_latent_segments(yr, np.stack([off[:-1], off[1:]], 1), tuning=tun)['log_marginal_final']
+    loop_walls = wall_all_ms(loop, 1, 0)
+    own = m.shuffle_test_segments(y, seg, n_shuffle=n_loop, shift=shift_d, tuning=tun)['log_marginal_shuffle']
+    per_shuffle = min(loop_walls) / n_loop
+    rec.update({"loop_shuffles_timed": n_loop, "loop_is_a_subset_scaled_to_n_shuffle": bool(n_loop < R),
+                "loop_per_shuffle_wall_ms": round(per_shuffle, 3), "loop_wall_ms_scaled": round(per_shuffle * R, 1),
+                "loop_over_one_call_median": round(per_shuffle * R / float(np.median(walls)), 2),
+                "loop_vs_one_call_bits_equal": bool(np.array_equal(looped, own))})
+    # the roll kernel alone against the route it replaces on the same rows
+    src = SpikeData(yc, None)
+    nb = min(8, n_loop)
+    off_d = torch.as_tensor(off, device=dev)
+    sh = shift_d[:nb].contiguous()
+    sp = SpikeData.rolled(src, off_d, sh)
+    lens = torch.as_tensor(np.diff(off), device=dev)
+    seg_of = torch.repeat_interleave(torch.arange(len(seg), device=dev), lens)
+    a_t, ln_t = off_d[:-1][seg_of][:, None], lens[seg_of][:, None]
+    rel = torch.arange(rows, device=dev)[:, None] - a_t
+    stacked = SpikeData(torch.zeros((nb * rows, N), dtype=torch.float32, device=dev), None)
+
+    def gather_refresh():
+        for r in range(nb):
+            idx = a_t + torch.remainder(rel - sh[r].long()[seg_of], ln_t)
+            stacked.y[r * rows:(r + 1) * rows] = torch.gather(src.y, 0, idx)
+        stacked.refresh()
+
+    def event_ms(fn, n=5):
+        out = []
+        for _ in range(n + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1))
+        return out[1:]
+    k_ms = event_ms(lambda: sp.roll(src, off_d, sh))
+    g_ms = event_ms(gather_refresh)
+    same = bool(torch.equal(sp.yq, stacked.yq) and torch.equal(sp.gconst.view(torch.int64),
+                                                                stacked.gconst.view(torch.int64)))
+    rec.update({"roll_kernel_copies": nb,
+                "roll_kernel_ms_all": [round(v, 4) for v in k_ms], "roll_kernel_ms_median": round(float(np.median(k_ms)), 4),
+                "roll_kernel_us_per_shuffle": round(1e3 * float(np.median(k_ms)) / nb, 2),
+                "gather_refresh_ms_all": [round(v, 4) for v in g_ms],
+                "gather_refresh_ms_median": round(float(np.median(g_ms)), 4),
+                "gather_refresh_over_roll_kernel": round(float(np.median(g_ms) / np.median(k_ms)), 2),
+                "roll_kernel_equals_gather_refresh_bits": same})
+    return rec
+
+
 def run_crossover(args, y, tun):
     table, best = [], 0
     for n in CROSSOVER_LENGTHS:
@@ -298,7 +406,8 @@ def main():
     ap.add_argument("--viterbi", action="store_true")
     ap.add_argument("--sample", type=int, default=0, metavar="R")
     ap.add_argument("--shuffle", type=int, default=0, metavar="R")
-    ap.add_argument("--shuffle-kind", default="time_bin", choices=("time_bin", "column_cycle", "both"))
+    ap.add_argument("--shuffle-kind", default="time_bin", choices=("time_bin", "column_cycle", "both", "neuron_circular"))
+    ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--loop-shuffles", type=int, default=50)
     ap.add_argument("--parent-json", default=None)
     ap.add_argument("--json", default=None)
@@ -309,6 +418,9 @@ def main():
     if args.crossover:
         rec = run_crossover(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_crossover_c3.json")
+    elif args.shuffle and args.shuffle_kind == "neuron_circular":
+        rec = run_neuron_shuffle(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_shuffle_bench_c3_neuron_circular.json")
     elif args.shuffle:
         rec = run_shuffle(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_shuffle_bench_c3.json")
