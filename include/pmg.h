@@ -609,6 +609,42 @@ int pmg_dense_backward_phase(const float* delta, const float* phi, const double*
                              int64_t T, const pmg_dense_transition* tr, double likelihood_scale, int32_t chunk,
                              int32_t warmup, double tol, float* P, float* gamma, float* log_gamma, float* rho,
                              double* log_rho, void* workspace, size_t workspace_bytes, void* stream, int32_t phase);
+/* Smoother of many short, independent chains (events) in one call on the dense        */
+/* log-domain scans: pmg_segment_smoother's ragged launch for every transition the      */
+/* banded scans do not hold (custom kernels, bands wider than PMG_MAX_BAND, the          */
+/* latent-only models, L in (1024, 4096]), with exact log outputs.  One 256-thread       */
+/* workgroup per segment walks it sequentially with the chain steps of                   */
+/* pmg_dense_forward / pmg_dense_backward, from the filters' own prior (a uniform        */
+/* (d, l) state pushed through one transition): no chunks, warm-up, verification or      */
+/* relaxation, hence no workspace, tol or chunk, no atomics and no wait between          */
+/* workgroups; a workgroup ends after twice its segment's rows.                          */
+/*   delta, phi, ll64, m, tr, likelihood_scale: exactly as pmg_dense_forward takes       */
+/*            them, for T gathered rows (ll64 may be NULL);                              */
+/*   seg_off, order: exactly as pmg_segment_smoother takes them (DEVICE CSR int64,       */
+/*            each segment clamped on the device to 0 <= a <= b <= T; workgroup w        */
+/*            takes segment order[w] (NULL: w); `order` changes scheduling only,         */
+/*            entries outside 0 .. S-1 are skipped).                                     */
+/* outputs: alpha (T,2,L) f32 or NULL, log_alpha (T,2,L) F64 (required: the backward     */
+/*          pass reads it back) and logc (T) f64 (required) as pmg_dense_forward;        */
+/*          gamma (T,2,L), log_gamma (T,2,L), P (T,L) f32 as pmg_dense_backward, each    */
+/*          may be NULL (all three NULL: only the filter runs);                          */
+/*          logz (S) f64, logz[s] = the segment's logc summed in time order from its     */
+/*          first row; an empty segment (a >= b) writes logz[s] = 0 and nothing else.    */
+/* Contracts: for every row a segment owns, all seven outputs equal bit for bit what      */
+/* pmg_dense_forward + pmg_dense_backward write on that segment's rows alone with         */
+/* chunk >= its length (one chunk: the same functions in the same order).  A segment's    */
+/* outputs depend on its own rows only: not on the other segments, their order,           */
+/* `order`, or whether a posterior output was asked for.  Rows that no clamped segment    */
+/* owns are not written.  (Segments that overlap after clamping race on their shared      */
+/* rows, within the buffers.)                                                             */
+/* PMG_EINVAL, before any HIP call, for a NULL delta, phi, m, seg_off, tr, log_alpha,     */
+/* logc or logz, T <= 0, S < 0 or a bad transition; PMG_EUNSUPPORTED for L > 4096.        */
+/* S = 0 is PMG_OK with no launch.                                                        */
+int pmg_dense_segment_smoother(const float* delta, const float* phi, const double* ll64, const double* m, int64_t T,
+                               const int64_t* seg_off, int32_t S, const int32_t* order,
+                               const pmg_dense_transition* tr, double likelihood_scale,
+                               float* alpha, double* log_alpha, float* gamma, float* log_gamma, float* P,
+                               double* logc, double* logz, void* stream);
 /* Pairwise joint in log space (decode, dense scans): logS (2L x 2L) f64 =           */
 /* LSE_{t<T-1} log_alpha_t[x] + log_rho_{t+1}[x'], x = (d,i) (f64 inputs, f64 online  */
 /* sum); the caller forms the log joint logA[d,d'] + logK[d',i,j] + logS               */

@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = (
     "pmg_joint_log_workspace_size", "pmg_joint_log_accumulate_ws", "pmg_posterior_outputs",
     "pmg_viterbi_workspace_size", "pmg_viterbi_decode", "pmg_segment_smoother",
     "pmg_segment_viterbi_workspace_size", "pmg_segment_viterbi", "pmg_segment_sample",
-    "pmg_segment_shuffle_logz", "pmg_segment_roll_prepare",
+    "pmg_segment_shuffle_logz", "pmg_segment_roll_prepare", "pmg_dense_segment_smoother",
 )
 
 
@@ -203,6 +203,8 @@ _SIGS = {
     "pmg_segment_shuffle_logz": ([_P, _P, _P, _I64, _P, _I32, _P, ctypes.POINTER(Transition), _D, _P, _P, _I32, _P, _P],
                                  _I32),
     "pmg_segment_roll_prepare": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P, _P], _I32),
+    "pmg_dense_segment_smoother": ([_P, _P, _P, _P, _I64, _P, _I32, _P, ctypes.POINTER(DenseTransition), _D,
+                                    _P, _P, _P, _P, _P, _P, _P, _P], _I32),
 }
 
 _lib = None

@@ -468,7 +468,7 @@ class PoissonGPLVMJump1D:
         return self._viterbi_result(pd, pl, lj, t_l)
 
     def decode_latent_segments(self, y, segments=None, tuning=None, hyperparam={}, ma_neuron=None,
-                               ma_latent=None, likelihood_scale=1.):
+                               ma_latent=None, likelihood_scale=1., exact=False):
         """Smooth many independent events (ripple or replay candidates, trials, epochs) in
         one call: each segment is a chain of its own, started from the filters' own prior
         (a uniform (d, l) state pushed through one transition), with no state carried
@@ -491,65 +491,102 @@ class PoissonGPLVMJump1D:
           log_likelihood_all (Ttot, L), log_marginal_final (S,) float64.
         The pairwise joint (p_transition_*) is not formed.  A transition that needs the dense
         scans (custom kernel, n_latent_bin > 1024, band > 32) raises NotImplementedError, and
-        bad intervals ValueError, before any device work."""
+        bad intervals ValueError, before any device work.
+
+        exact=True runs the dense log-domain scans instead, as decode_latent does by default
+        (ScanConfig.decode_exact), with one 256-thread workgroup per event
+        (pmg_dense_segment_smoother): any transition with n_latent_bin <= 4096 (a
+        custom_transition_kernel, a movement kernel wider than 32 bins, more than 1024
+        latents), the values not limited by float32's floor.  It adds the key
+        log_posterior_all (Ttot, 2, L), the exact log posteriors, and takes
+        log_causal_posterior_all from the float64 log filter state.  An event longer than
+        min(scan_config.segment_wave_max, scan_config.segment_dense_max) rows goes to the
+        chunk-parallel dense scans on its own.  n_latent_bin > 4096 raises NotImplementedError
+        before any device work."""
+        if not isinstance(exact, (bool, np.bool_)):
+            raise TypeError(f"exact must be a bool, got {exact!r}")
+        exact = bool(exact)
         hp, _, yc, off, ma, tuning, ma_latent = self._segments_prologue(
-            y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'decode_latent_segments')
+            y, segments, tuning, hyperparam, ma_neuron, ma_latent, 'decode_latent_segments', exact=exact)
         S, Ttot, L = len(off) - 1, int(off[-1]), self.n_latent_bin
-        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=False)
+        eng = self._decode_engine(yc, tuning, hp, ma, ma_latent, exact=exact)
         dev = eng.dev
         cp = _PinnedCopies(dev)
         for key, shape in (('lcaus', (Ttot, 2, L)), ('gamma', (Ttot, 2, L)), ('ll', (Ttot, L)), ('plm', (Ttot, L))):
             cp.reserve(key, shape)
         gamma = torch.empty((Ttot, 2, L), dtype=torch.float32, device=dev)
+        lgam = torch.empty((Ttot, 2, L), dtype=torch.float32, device=dev) if exact else None
         logz = torch.empty(S, dtype=torch.float64, device=dev)
-        self._segments_scan(eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz, gamma)
+        self._segments_scan(eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz, gamma, lgam)
         ml = None if ma_latent is None else np.asarray(ma_latent).astype(bool)
         _, plm, pdm = posterior_outputs(gamma, log=False)
-        h_lcaus = cp.submit(log_of(eng.alpha), key='lcaus')
+        h_lcaus = cp.submit(eng.log_alpha.to(torch.float32) if exact else log_of(eng.alpha), key='lcaus')
         h_gamma = cp.submit(gamma, key='gamma')
         h_plm = cp.submit(plm, key='plm')
         h_pdm = cp.submit(pdm)
         h_logc = cp.submit(eng.logc.to(torch.float32))
         h_ll = cp.submit(eng.loglik(), key='ll')
         h_lz = cp.submit(logz)
+        h_lpost = cp.submit(lgam) if exact else None
         cp.finish()
-        return {'segment_offsets': off,
-                'posterior_all': h_gamma,
-                'posterior_latent_marg': h_plm,
-                'posterior_dynamics_marg': h_pdm,
-                'log_causal_posterior_all': _masked_log(h_lcaus, ml),
-                'log_one_step_predictive_marginals_all': h_logc,
-                'log_likelihood_all': h_ll,
-                'log_marginal_final': h_lz}
+        res = {'segment_offsets': off,
+               'posterior_all': h_gamma,
+               'posterior_latent_marg': h_plm,
+               'posterior_dynamics_marg': h_pdm,
+               'log_causal_posterior_all': _masked_log(h_lcaus, ml),
+               'log_one_step_predictive_marginals_all': h_logc,
+               'log_likelihood_all': h_ll,
+               'log_marginal_final': h_lz}
+        if exact:
+            res['log_posterior_all'] = _masked_log(h_lpost, ml)
+        return res
 
-    def _segments_scan(self, eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz, gamma=None):
+    def _segments_scan(self, eng, yc, off, ma, tuning, hp, ma_latent, likelihood_scale, logz, gamma=None,
+                       log_gamma=None):
         """The scans of decode_latent_segments / sample_latent_segments over the compact rows
         of `eng`: emission, then every run of consecutive one-wave segments in one
         segment_smoother call and every event longer than scan_config.segment_wave_max on the
         chunk-parallel scans of an engine of its own, spliced into eng.alpha / eng.logc.
-        gamma (Ttot, 2, L) device tensor: filter and smooth; None: the filter alone."""
+        gamma (Ttot, 2, L) device tensor: filter and smooth; None: the filter alone.
+        An engine that holds a dense transition (decode_latent_segments(exact=True)) takes the
+        same two routes on the dense log-domain scans: one workgroup per segment
+        (segment_smoother_dense), a longer event on the chunk-parallel dense scans, with
+        eng.log_alpha spliced as well and the exact log posteriors in log_gamma (Ttot, 2, L)."""
         dev = eng.dev
+        dense = bool(eng.dense)
+        if log_gamma is not None and (not dense or gamma is None):
+            raise ValueError("log_gamma is produced by the dense scans, together with gamma")
         eng.emission(likelihood_scale)
-        short = np.diff(off) <= int(self.scan_config.segment_wave_max)
+        longest = int(self.scan_config.segment_wave_max)
+        if dense:
+            longest = min(longest, int(self.scan_config.segment_dense_max))
+        short = np.diff(off) <= longest
         for i0, i1 in _true_runs(short):       # consecutive one-wave segments: one call per run
             r0, r1 = int(off[i0]), int(off[i1])
             rel = off[i0:i1 + 1] - r0
-            _, _, lz = eng.segment_smoother(likelihood_scale, torch.as_tensor(rel, device=dev),
-                                            torch.as_tensor(segment_order(rel), device=dev),
-                                            gamma=None if gamma is None else gamma[r0:r1], rows=(r0, r1))
+            seg = (likelihood_scale, torch.as_tensor(rel, device=dev), torch.as_tensor(segment_order(rel), device=dev))
+            out = {'gamma': None if gamma is None else gamma[r0:r1], 'rows': (r0, r1)}
+            if dense:
+                _, _, lz = eng.segment_smoother_dense(
+                    *seg, log_gamma=None if log_gamma is None else log_gamma[r0:r1], **out)
+            else:
+                _, _, lz = eng.segment_smoother(*seg, **out)
             logz[i0:i1] = lz
         for i in np.flatnonzero(~short):        # the chunk-parallel scans, one segment at a time
             a, b = int(off[i]), int(off[i + 1])
             sub = self._decode_engine(yc[a:b], tuning, hp, ma[a:b] if np.ndim(ma) == 2 else ma, ma_latent,
-                                      exact=False)
+                                      exact=dense)
             if gamma is None:
                 sub.emission(likelihood_scale)
                 sub.forward(likelihood_scale, logz[i:i + 1], keep_alpha=True)
             else:
-                sub.e_step(likelihood_scale, logz[i:i + 1], gamma=gamma[a:b])
+                sub.e_step(likelihood_scale, logz[i:i + 1], gamma=gamma[a:b],
+                           log_gamma=None if log_gamma is None else log_gamma[a:b])
             sub.check_status()
             eng.alpha[a:b].copy_(sub.alpha)
             eng.logc[a:b].copy_(sub.logc)
+            if dense:
+                eng.log_alpha[a:b].copy_(sub.log_alpha)
         eng.check_status()
 
     def sample_latent_segments(self, y, segments=None, n_samples=100, key=0, uniforms=None, tuning=None,
@@ -855,16 +892,24 @@ class PoissonGPLVMJump1D:
         res.update(self._viterbi_result(_np(pd), _np(pl), _np(lj)))
         return res
 
-    def _segments_prologue(self, y, segments, tuning, hyperparam, ma_neuron, ma_latent, what, check=None):
+    def _segments_prologue(self, y, segments, tuning, hyperparam, ma_neuron, ma_latent, what, check=None,
+                           exact=False):
         """The host half the segment methods open with: the hyper-parameters, the banded
         transition (NotImplementedError for a dense one), the caller's own argument `check`,
         the defaults and the gathered rows (ValueError for bad intervals), in that order.  No
         device work: the caller makes its remaining host checks, then its engine.  Returns
-        (hp, tr, yc, off, ma, tuning, ma_latent)."""
+        (hp, tr, yc, off, ma, tuning, ma_latent).  exact: the dense log-domain scans take any
+        transition up to 4096 latents, so there is no banded one to build (tr is None)."""
         if _is_tsd(y):
             y = y.d
         hp, _, _ = self._dynamics_decode_args(self._decode_hp(hyperparam))
-        tr = self._map_transition(hp, what)
+        if exact:
+            if self.n_latent_bin > 4096:
+                raise NotImplementedError(f"{what}: n_latent_bin={self.n_latent_bin} > 4096 is beyond the dense "
+                                          "log-domain scans")
+            tr = None
+        else:
+            tr = self._map_transition(hp, what)
         if check is not None:
             check()
         if ma_neuron is None:
@@ -1897,13 +1942,29 @@ class PoissonGPLVM1D(PoissonGPLVMJump1D):
         r = self._run_decode(y, tuning, hp, ma_neuron, ma_latent, likelihood_scale, joint=True, logK=logK, logA=logA)
         return self._decode_result(r, t_l)
 
-    def decode_latent_segments(self, y, segments=None, **kwargs):
-        """Not available: the one-wave segment smoother runs the banded linear-space scans,
-        and a chain without a jump path is ill-conditioned in float32 (see _transition: the
-        latent-only models always take the dense log-domain scans)."""
-        raise NotImplementedError(f"{type(self).__name__}.decode_latent_segments: the latent-only models need the "
-                                  "dense log-domain scans, which the segment smoother does not run; call "
-                                  "decode_latent once per segment")
+    def decode_latent_segments(self, y, segments=None, exact=False, **kwargs):
+        """With exact=True only: the one-wave segment smoother of the default runs the banded
+        linear-space scans, and a chain without a jump path is ill-conditioned in float32
+        (see _transition: the latent-only models always take the dense log-domain scans).
+        exact=True smooths every event on those scans, one workgroup per event, and returns
+        the d = 0 block as decode_latent does: segment_offsets, posterior_all (Ttot, L),
+        log_posterior_all (Ttot, L), log_causal_posterior_all (Ttot, L),
+        log_one_step_predictive_marginals_all (Ttot,), log_likelihood_all (Ttot, L) and
+        log_marginal_final (S,)."""
+        if not isinstance(exact, (bool, np.bool_)):
+            raise TypeError(f"exact must be a bool, got {exact!r}")
+        if not exact:
+            raise NotImplementedError(f"{type(self).__name__}.decode_latent_segments: the latent-only models need "
+                                      "the dense log-domain scans, which the default segment smoother does not "
+                                      "run; pass exact=True")
+        r = super().decode_latent_segments(y, segments, exact=True, **kwargs)
+        return {'segment_offsets': r['segment_offsets'],
+                'posterior_all': r['posterior_all'][:, 0],
+                'log_posterior_all': r['log_posterior_all'][:, 0],
+                'log_causal_posterior_all': r['log_causal_posterior_all'][:, 0],
+                'log_one_step_predictive_marginals_all': r['log_one_step_predictive_marginals_all'],
+                'log_likelihood_all': r['log_likelihood_all'],
+                'log_marginal_final': r['log_marginal_final']}
 
     def sample_latent_segments(self, y, segments=None, **kwargs):
         """Not available, for the reason decode_latent_segments gives: the sampler draws from

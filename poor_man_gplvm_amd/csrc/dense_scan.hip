@@ -23,6 +23,7 @@
 
 #include "pmg_common.h"
 #include "pmg_math64.h"
+#include "segment_table.h"
 
 #pragma clang fp contract(on)
 
@@ -1128,6 +1129,73 @@ static void dense_kernels(int JD, dense_kernel_t* f, dense_kernel_t* fr, dense_k
   }
 }
 
+// ---------------------------------------------------------------------------
+// Many short, independent chains (events) in one launch: workgroup w walks segment
+// order[w] of a CSR of rows sequentially and exactly, with the chain steps above --
+// init_uniform + dfwd_run over [a, b), then init_ones + dbwd_out over [a, b) with no
+// later step (has_prev false): what k_dense_forward / k_dense_backward run for a
+// sequence that is one chunk (c = 0 = M - 1: nothing to warm up, verify or repair), so a
+// segment's outputs equal theirs on its rows alone bit for bit.  No workspace, no
+// atomic, no wait on another workgroup: the kernel ends after 2 (b - a) steps.
+//
+// Rows: seg_rows clamps the segment to 0 <= a <= b <= T, and dfwd_run / dbwd_out index
+// rows t in [a, b) only (the rho stores at t + 1 are off: rho and log_rho are null).
+// The backward pass reads log_alpha[t, d, j] for j = tid + 256 k, the elements this
+// thread stored itself in the forward pass, so no fence or barrier orders them.
+// The LDS operand buffer is indexed by the row number's parity (t & 1 in dfwd_run /
+// dbwd_out), not by t - a: which of the two buffers a step uses changes no value, only
+// that consecutive steps alternate, which holds for any a.  The forward's last step and
+// the backward's first step_back may share a buffer; the barriers of the block LSEs
+// between them (the forward's normaliser, the backward's G and V) order that reuse, and
+// the same barriers separate the last use of a reduction slot by the forward chain from
+// the backward chain's first (its own Slots start over at 0).
+// ---------------------------------------------------------------------------
+struct DenseSegParams {
+  DenseParams p;   // emission, transition and outputs (log_alpha_in = log_alpha)
+  SegTable seg;    // the segments' rows (seg_off set)
+  double* logz;    // (S)
+  int smooth;      // a posterior output was asked for: run the backward pass
+};
+
+template <int JD>
+__global__ void __launch_bounds__(kDNT) k_dense_segment(DenseSegParams sp) {
+  __shared__ DenseShared<JD> sh;
+  const DenseParams& p = sp.p;
+  int s;
+  int64_t t_a, t_b;
+  __builtin_assume(sp.seg.seg_off != nullptr);   // the ragged set only
+  if (!seg_rows(sp.seg, p.T, blockIdx.x, s, t_a, t_b)) return;   // workgroup-uniform
+  if (t_a >= t_b) {
+    if (threadIdx.x == 0) sp.logz[s] = 0.0;
+    return;
+  }
+  {
+    DFwd<JD> st;
+    st.init_uniform(p);
+    const double lz = dfwd_run<JD, true>(p, st, sh, t_a, t_b);
+    if (threadIdx.x == 0) sp.logz[s] = lz;
+  }
+  if (!sp.smooth) return;
+  DBwd<JD> st;
+  st.init_ones(p);
+  double vp0[JD], vp1[JD];
+#pragma unroll
+  for (int k = 0; k < JD; ++k) vp0[k] = vp1[k] = -INFINITY;
+  dbwd_out<JD>(p, st, sh, t_a, t_b, vp0, vp1, false);
+}
+
+typedef void (*dense_segment_kernel_t)(DenseSegParams);
+
+static dense_segment_kernel_t dense_segment_kernel(int JD) {
+  switch (JD) {
+    case 1: return k_dense_segment<1>;
+    case 2: return k_dense_segment<2>;
+    case 4: return k_dense_segment<4>;
+    case 8: return k_dense_segment<8>;
+    default: return k_dense_segment<16>;
+  }
+}
+
 }  // namespace pmg
 
 using namespace pmg;
@@ -1337,6 +1405,71 @@ int pmg_joint_log_accumulate_ws(const double* log_alpha, const double* log_rho, 
 int pmg_joint_log_accumulate(const double* log_alpha, const double* log_rho, int64_t T, int32_t L, double* logS,
                              void* stream) {
   return pmg_joint_log_accumulate_ws(log_alpha, log_rho, T, L, logS, nullptr, 0, stream);
+}
+
+int pmg_dense_segment_smoother(const float* delta, const float* phi, const double* ll64, const double* m, int64_t T,
+                               const int64_t* seg_off, int32_t S, const int32_t* order,
+                               const pmg_dense_transition* tr, double likelihood_scale, float* alpha,
+                               double* log_alpha, float* gamma, float* log_gamma, float* P, double* logc,
+                               double* logz, void* stream) {
+  // every refusal comes before the first HIP call (so also without a device)
+  PMG_REQUIRE(T > 0, "pmg_dense_segment_smoother: T=%lld must be > 0", (long long)T);
+  PMG_REQUIRE(S >= 0, "pmg_dense_segment_smoother: S=%d segments (>= 0)", S);
+  PMG_REQUIRE(delta, "pmg_dense_segment_smoother: delta is null");
+  PMG_REQUIRE(phi, "pmg_dense_segment_smoother: phi is null");
+  PMG_REQUIRE(m, "pmg_dense_segment_smoother: m is null");
+  PMG_REQUIRE(seg_off, "pmg_dense_segment_smoother: seg_off is null");
+  PMG_REQUIRE(tr && tr->L > 0 && tr->logK && tr->logKT && tr->logK_lo && tr->logKT_lo,
+              "pmg_dense_segment_smoother: bad transition");
+  PMG_REQUIRE(likelihood_scale == likelihood_scale, "pmg_dense_segment_smoother: likelihood_scale is NaN");
+  PMG_REQUIRE(log_alpha, "pmg_dense_segment_smoother: log_alpha is null");
+  PMG_REQUIRE(logc, "pmg_dense_segment_smoother: logc is null");
+  PMG_REQUIRE(logz, "pmg_dense_segment_smoother: logz is null");
+  const int JD = dense_jd(tr->L);
+  if (JD < 0) {
+    set_error("pmg_dense_segment_smoother: L=%d > 4096 unsupported", tr->L);
+    return PMG_EUNSUPPORTED;
+  }
+  if (S == 0) return PMG_OK;
+  // the fields the chain steps read (dense_params without the chunk grid, which would ask
+  // the device for its CU count)
+  DenseSegParams sp;
+  memset(&sp, 0, sizeof(sp));
+  DenseParams& p = sp.p;
+  p.delta = delta;
+  p.phi = phi;
+  p.ll64 = ll64;
+  p.m = m;
+  p.T = T;
+  p.L = tr->L;
+  p.nblk = (int)(round_up(tr->L, 32) / 32);
+  p.Lp = kDNT * JD;
+  p.K = tr->logK;
+  p.KT = tr->logKT;
+  p.Klo = tr->logK_lo;
+  p.KTlo = tr->logKT_lo;
+  p.lA00 = tr->logA[0];
+  p.lA01 = tr->logA[1];
+  p.lA10 = tr->logA[2];
+  p.lA11 = tr->logA[3];
+  p.logL = logf((float)tr->L);
+  p.s = (float)likelihood_scale;
+  p.s_d = likelihood_scale;
+  p.alpha = alpha;
+  p.log_alpha = log_alpha;
+  p.log_alpha_in = log_alpha;
+  p.logc = logc;
+  p.gamma = gamma;
+  p.log_gamma = log_gamma;
+  p.P = P;
+  sp.seg.seg_off = seg_off;
+  sp.seg.order = order;
+  sp.seg.S = S;
+  sp.logz = logz;
+  sp.smooth = (gamma || log_gamma || P) ? 1 : 0;
+  hipLaunchKernelGGL(dense_segment_kernel(JD), dim3(S), dim3(kDNT), 0, as_stream(stream), sp);
+  PMG_LAUNCH_CHECK();
+  return PMG_OK;
 }
 
 }  // extern "C"

@@ -93,6 +93,17 @@ class ScanConfig:
                                   # 6.0 against 6.8 ms per call at 1024 rows, 11.8 against 8.0 ms at 4096
                                   # (one wave takes ~1.35 us per row, the chunk-parallel route pays a second
                                   # engine and emission; profiles/segments_crossover_c3.json)
+    segment_dense_max: int = 128  # decode_latent_segments(exact=True): a segment of up to
+                                  # min(segment_wave_max, segment_dense_max) rows is walked by one workgroup of
+                                  # pmg_dense_segment_smoother; a longer one goes to the chunk-parallel dense
+                                  # scans on its own.  The largest power of two at which one workgroup was not
+                                  # slower for a single segment at the C3 shape: 28.5 against 32.1 ms per call at
+                                  # 128 rows, 47.2 against 32.4 ms at 256 (a lone workgroup takes ~146 us per row
+                                  # for both passes at L = 512, the chunk-parallel route a flat ~16 ms of kernels
+                                  # plus a second engine; profiles/segments_exact_crossover_c3.json).  A batch
+                                  # whose few longest events lie just above it can be faster with a larger value:
+                                  # each such event then costs its rows on one workgroup beside the others
+                                  # instead of a call of its own (profiles/segments_exact_bench_c3.json)
 
     def chunk_for(self, T):
         if self.chunk:
@@ -1083,6 +1094,41 @@ class DeviceEM(EngineBase):
                                                     nat.ptr(logz), nat.stream_handle()), "pmg_segment_smoother")
         self.alpha_bits = 0
         return alpha, logc, logz
+
+    def _need_dense(self, what):
+        if not self.dense:
+            raise NotImplementedError(f"{what} needs a dense transition (set_transition with a DenseTransition)")
+
+    def segment_smoother_dense(self, likelihood_scale, seg_off, order=None, gamma=None, log_gamma=None, P=None,
+                               rows=None):
+        """segment_smoother on the dense log-domain scans (pmg_dense_segment_smoother: one
+        256-thread workgroup per segment, exact and sequential), after emission() with the same
+        likelihood_scale.  seg_off, order, rows: as segment_smoother takes them; gamma,
+        log_gamma (T, 2, L) / P (T, L) float32 device outputs or None (all None: the filter
+        alone).  Returns device tensors (log_alpha (T, 2, L) float64 -- the engine's buffer --,
+        logc (T,), logz (S,) float64); the engine's alpha holds exp(log_alpha) on the same rows,
+        and rows that no segment owns are left as they were."""
+        self._need_dense("segment_smoother_dense")
+        r0, r1 = (0, self.T) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 < r1 <= self.T:
+            raise ValueError(f"rows {(r0, r1)} outside [0, {self.T}]")
+        T = r1 - r0
+        S = self._n_segments(seg_off, order)
+        for name, t, shape in (('gamma', gamma, (T, 2, self.L)), ('log_gamma', log_gamma, (T, 2, self.L)),
+                               ('P', P, (T, self.L))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
+                raise ValueError(f"{name} must be a {shape} float32 device tensor")
+        logz = torch.empty(S, dtype=torch.float64, device=self.dev)
+        log_alpha, logc = self.log_alpha[r0:r1], self.logc[r0:r1]
+        ll64 = None if self.ll64 is None else self.ll64[r0:r1]
+        with self._t('segment_smoother_dense'):
+            nat.check(self.lib.pmg_dense_segment_smoother(
+                nat.ptr(self.delta[r0:r1]), nat.ptr(self.phi[r0:r1]), nat.ptr(ll64), nat.ptr(self.mref[r0:r1]), T,
+                nat.ptr(seg_off), S, nat.ptr(order), ctypes.byref(self._tr_d), float(likelihood_scale),
+                nat.ptr(self.alpha[r0:r1]), nat.ptr(log_alpha), nat.ptr(gamma), nat.ptr(log_gamma), nat.ptr(P),
+                nat.ptr(logc), nat.ptr(logz), nat.stream_handle()), "pmg_dense_segment_smoother")
+        self.alpha_bits = 0
+        return log_alpha, logc, logz
 
     def segment_viterbi(self, likelihood_scale, seg_off, order=None):
         """Most likely (dynamics, latent) path of every independent segment of the rows in

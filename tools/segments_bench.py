@@ -45,7 +45,20 @@ and, for the roll kernel alone, the route it replaces on the same rows -- a segm
 gather of f32 y into the stacked tensor, then SpikeData.refresh() -- with the two routes' yq and
 gconst compared bit for bit.  Device time per kernel comes from running this tool under
 rocprofv3 --kernel-trace --stats (--no-loop skips everything but the one call).  Written to
-profiles/segments_shuffle_bench_c3_neuron_circular.json.  No ratio is fixed."""
+profiles/segments_shuffle_bench_c3_neuron_circular.json.  No ratio is fixed.
+
+--exact: the same event set through decode_latent_segments(exact=True) (the dense log-domain
+scans, one workgroup per event): every timed call's wall time, device time by section (the
+kernel is the segment_smoother_dense section), next to the only route without it, a loop of
+decode_latent calls over the first --loop-events events (default 30) scaled to S; the largest
+difference between the two, and whether the events of up to 64 rows (which the public loop runs
+as a single chunk too) are equal bit for bit.  Written to profiles/segments_exact_bench_c3.json.
+No ratio is fixed.
+
+--exact --crossover: one event of 16 .. 2048 rows through both routes of
+decode_latent_segments(exact=True) -- one workgroup and the chunk-parallel dense scans -- and
+the largest power of two at which one workgroup is not slower; written to
+profiles/segments_exact_crossover_c3.json.  ScanConfig.segment_dense_max cites it."""
 import argparse
 import json
 import os
@@ -374,6 +387,96 @@ def run_neuron_shuffle(args, y, tun):
     return rec
 
 
+EXACT_CROSSOVER_LENGTHS = (16, 32, 64, 128, 256, 512, 1024, 2048)
+EXACT_KEYS = ('posterior_all', 'log_posterior_all', 'log_one_step_predictive_marginals_all')
+
+
+def run_exact(args, y, tun):
+    """decode_latent_segments(exact=True) against the only route without it: a loop of
+    decode_latent calls, one per event (timed on the first --loop-events events, scaled)."""
+    seg = event_intervals(args.events, y.shape[0])
+    lens = seg[:, 1] - seg[:, 0]
+    m = model()
+    walls = wall_all_ms(lambda: m.decode_latent_segments(y, seg, tuning=tun, exact=True), args.calls, args.warmup)
+    timer = KernelTimer()
+    res = model(timer).decode_latent_segments(y, seg, tuning=tun, exact=True)
+    kern = sections_ms(timer)
+    # the same call with every event on one workgroup, whatever its length (the default sends
+    # the events beyond ScanConfig.segment_dense_max rows to the chunk-parallel dense scans)
+    big = 1 << 30
+    m_all = model(segment_wave_max=big, segment_dense_max=big)
+    walls_all = wall_all_ms(lambda: m_all.decode_latent_segments(y, seg, tuning=tun, exact=True), args.calls,
+                            args.warmup)
+    timer_all = KernelTimer()
+    model(timer_all, segment_wave_max=big, segment_dense_max=big).decode_latent_segments(y, seg, tuning=tun, exact=True)
+    kern_all = sections_ms(timer_all)
+    n_loop = min(int(args.loop_events), len(seg))
+    singles = []
+
+    def loop():
+        singles[:] = [m.decode_latent(y[a:b], tuning=tun) for a, b in seg[:n_loop]]
+    loop_walls = wall_all_ms(loop, 1, 0)
+    per_event = min(loop_walls) / n_loop
+    off = res['segment_offsets']
+    same, diff, lz_rel = [], 0.0, 0.0
+    for s, r in enumerate(singles):
+        sl = slice(int(off[s]), int(off[s + 1]))
+        same.append(bool(all(np.array_equal(r[k], res[k][sl]) for k in EXACT_KEYS)
+                         and r['log_marginal_final'] == res['log_marginal_final'][s]))
+        diff = max(diff, float(np.abs(r['posterior_all'].astype(np.float64) - res['posterior_all'][sl]).max()))
+        lz_rel = max(lz_rel, abs(r['log_marginal_final'] - res['log_marginal_final'][s]) / abs(r['log_marginal_final']))
+    short = lens[:n_loop] <= 64      # the public loop runs these as a single chunk too
+    k_ms = kern.get("segment_smoother_dense", 0.0)
+    rows = int(lens.sum())
+    return {"shape": "c3", "N": N, "L": L, "events": int(len(seg)), "rows": rows,
+            "mean_length": round(float(lens.mean()), 2), "max_length": int(lens.max()),
+            "decode_latent_segments_exact_wall_ms": round(min(walls), 3),
+            "decode_latent_segments_exact_wall_ms_all": [round(w, 3) for w in walls],
+            "decode_latent_segments_exact_kernel_ms": kern, "kernel_ms_total": round(sum(kern.values()), 4),
+            "segment_smoother_dense_ms": round(k_ms, 4),
+            "segment_smoother_dense_us_per_row": round(1e3 * k_ms / rows, 4),
+            "segment_dense_max": int(m.scan_config.segment_dense_max),
+            "events_beyond_segment_dense_max": int((lens > m.scan_config.segment_dense_max).sum()),
+            "all_on_one_workgroup_wall_ms_all": [round(w, 3) for w in walls_all],
+            "all_on_one_workgroup_kernel_ms": kern_all,
+            "decode_latent_per_event_wall_ms": round(per_event, 3), "loop_events_timed": n_loop,
+            "decode_latent_loop_wall_ms_scaled": round(per_event * len(seg), 1),
+            "loop_over_one_call": round(per_event * len(seg) / min(walls), 1),
+            "loop_vs_call_max_abs_posterior_diff": diff, "loop_vs_call_max_rel_logz_diff": lz_rel,
+            "loop_events_up_to_64_rows": int(short.sum()),
+            "loop_events_up_to_64_rows_equal_bit_for_bit": bool(np.all(np.asarray(same)[short])),
+            "loop_events_equal_bit_for_bit": int(np.sum(same))}
+
+
+def run_exact_crossover(args, y, tun):
+    """One event of n rows through both routes of decode_latent_segments(exact=True): one
+    workgroup (both segment limits above the length) and the chunk-parallel dense scans
+    (segment_wave_max = 1)."""
+    table, best = [], 0
+    big = 1 << 30
+    for n in EXACT_CROSSOVER_LENGTHS:
+        seg = np.array([[0, n]])
+        row = {"length": n}
+        for name, scan in (("one_workgroup", dict(segment_wave_max=big, segment_dense_max=big)),
+                           ("chunk_parallel", dict(segment_wave_max=1))):
+            timer = KernelTimer()
+            m = model(timer, **scan)
+            row[name + "_wall_ms"] = round(wall_ms(lambda: m.decode_latent_segments(y, seg, tuning=tun, exact=True),
+                                                   args.calls, args.warmup), 3)
+            timer.reset()
+            m.decode_latent_segments(y, seg, tuning=tun, exact=True)
+            row[name + "_kernel_ms"] = sections_ms(timer)
+        table.append(row)
+    for row in table:           # the largest length up to which one workgroup was never slower
+        if row["one_workgroup_wall_ms"] <= row["chunk_parallel_wall_ms"]:
+            best = row["length"]
+        else:
+            break
+    return {"shape": "c3", "N": N, "L": L, "table": table, "one_workgroup_not_slower_up_to": best,
+            "rule": "wall time of one decode_latent_segments(exact=True) call, best of --calls; lengths are "
+                    "powers of two"}
+
+
 def run_crossover(args, y, tun):
     table, best = [], 0
     for n in CROSSOVER_LENGTHS:
@@ -404,6 +507,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--crossover", action="store_true")
     ap.add_argument("--viterbi", action="store_true")
+    ap.add_argument("--exact", action="store_true")
+    ap.add_argument("--loop-events", type=int, default=30)
     ap.add_argument("--sample", type=int, default=0, metavar="R")
     ap.add_argument("--shuffle", type=int, default=0, metavar="R")
     ap.add_argument("--shuffle-kind", default="time_bin", choices=("time_bin", "column_cycle", "both", "neuron_circular"))
@@ -415,7 +520,13 @@ def main():
     T = bench.CONFIGS["c3"][1]
     y, B, W0, _ = bench.synth(N, T, L)
     tun = np.logaddexp(B.astype(np.float64) @ W0.astype(np.float64), 0.0)
-    if args.crossover:
+    if args.exact and args.crossover:
+        rec = run_exact_crossover(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_exact_crossover_c3.json")
+    elif args.exact:
+        rec = run_exact(args, y, tun)
+        path = args.json or os.path.join(ROOT, "profiles", "segments_exact_bench_c3.json")
+    elif args.crossover:
         rec = run_crossover(args, y, tun)
         path = args.json or os.path.join(ROOT, "profiles", "segments_crossover_c3.json")
     elif args.shuffle and args.shuffle_kind == "neuron_circular":
